@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Bench of the ESLAM rendering hot path on MI355X (contract: one JSON line on stdout from rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the line: metric / value / unit / ms_per_step of the timed steps, and
+the workload's description.  --full adds everything else measured after the timed region (step percentiles, per-kernel
+times and the roofline, eager / NCHW / trained-state / forward-only side measurements, the unsharded strong-scaling
+comparison, the CPU and torch-on-GPU baselines).  --dump-outputs DIR writes what the last timed step computed, the loss and
+the gradient of every parameter, as DIR/<name>.npy (float32; inputs and seeds are fixed, so two builds can be compared
+array for array; arrays are sampled at fixed seeded positions if the whole set exceeds 64 MB).
 
 A "step" is one mapping iteration minus the optimiser update: depth-guided sampling ->
 render_batch_ray forward -> mapping loss -> backward to the 12 planes and the decoders, float32, inputs resident in HBM.
@@ -61,14 +68,21 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure percentiles, per-kernel times / roofline, side measurements and baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and parameter gradients as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU / torch-on-GPU baselines")
+    ap.add_argument("--profile-iters", type=int, default=20, help="--full: eager steps of the per-kernel profile")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch eagerly from Python (no hipGraph)")
     ap.add_argument("--weak", action="store_true", help="N > 1: every rank renders its own 4096 x 64 room0 batch")
     ap.add_argument("--strong", action="store_true", help="N = 1: run the configs[3] workload of the N > 1 mode unsharded")
-    ap.add_argument("--no-extras", action="store_true", help="skip eager / NCHW / forward-only side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip eager / NCHW / forward-only side measurements")
     ap.add_argument("--lowp", action="store_true", help="N = 1: BASELINE configs[4], the mixed-precision kernels on freiburg1_desk 5000 x 56")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def lib_hash():
@@ -114,6 +128,51 @@ def timed_median(fn, n, warm, reps=5):
     for _ in range(warm):
         fn()
     return sorted(timed(fn, n, 0) for _ in range(reps))[reps // 2]
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6       # --dump-outputs: all files together
+# the reference's names of the six plane groups (src/ESLAM.py init_planes), two resolutions each
+PLANE_GROUPS = ("planes_xy", "planes_xz", "planes_yz", "c_planes_xy", "c_planes_xz", "c_planes_yz")
+
+
+def step_outputs(loss, planes, decoders, params, grads=None):
+    """name -> tensor: what a caller of the timed step holds after it - the loss and the gradient of every parameter
+    (grads: the gradients in the order of params, when they do not sit in p.grad)."""
+    names = {}
+    for g, grp in enumerate(planes):
+        for i, p in enumerate(grp):
+            names[id(p)] = f"grad_{PLANE_GROUPS[g]}_{i}"
+    for n, p in decoders.named_parameters():
+        names[id(p)] = "grad_decoders_" + n.replace(".", "_")
+    outs = {"loss": loss.detach()}
+    for k, (p, g) in enumerate(zip(params, [p.grad for p in params] if grads is None else grads)):
+        if g is not None:
+            outs[names.get(id(p), f"grad_param_{k:02d}")] = g.detach()
+    return outs
+
+
+def dump_outputs(outs, folder, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every tensor as folder/<name>.npy, float32 (float64 stays float64), in its logical (NCHW) shape.  If the whole
+    set exceeds `budget` bytes, every array of more than 2^20 elements is replaced by its values at a fixed, seeded, ascending
+    choice of flat positions - the same fraction of each - so that the files fit.  Returns the bytes of data written."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    arrs = {}
+    for name, t in outs.items():
+        t = t.detach()
+        arrs[name] = (t if t.dtype == torch.float64 else t.float()).cpu().contiguous().numpy()
+    big = sorted(n for n, a in arrs.items() if a.size > 1 << 20)
+    total = sum(a.nbytes for a in arrs.values())
+    if total + 256 * len(arrs) > budget and big:
+        fixed = total - sum(arrs[n].nbytes for n in big)
+        frac = (budget - fixed - 256 * len(arrs)) / (total - fixed)          # (256 B per file: room for the .npy header)
+        for i, n in enumerate(big):
+            a = arrs[n].reshape(-1)
+            pick = np.random.default_rng(seed + i).choice(a.size, int(a.size * frac), replace=False)
+            arrs[n] = a[np.sort(pick)]
+    for name, a in arrs.items():
+        np.save(os.path.join(folder, name + ".npy"), a)
+    return sum(a.nbytes for a in arrs.values())
 
 
 def cpu_baseline(wl, budget_s=25.0, max_iters=5):
@@ -432,7 +491,7 @@ def run():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss = step()
     if mapper is not None and graphed:
         mapper.flush()
     fence()
@@ -448,15 +507,19 @@ def run():
         total_rays = wl.R
     ms_step = dt / args.steps * 1e3
     value = total_rays * wl.S / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the gradients are those of the last timed step (after an all-reduce: the job's)
+        if mapper is not None:       # (a replayed graph leaves p.grad as the capture left it: the gradients are the flat buffer's views)
+            outs = step_outputs(mapper.loss, mapper.planes, mapper.decoders, mapper.params, mapper.grads.views)
+        else:
+            outs = step_outputs(loss, wl.planes, wl.decoders, wl.params())
+        dump_outputs(outs, args.dump_outputs)
 
     out = None
     prof = None
-    if mapper is not None:           # the sharded step contains collectives: every rank takes part in the profiled steps
+    if args.full and mapper is not None:   # the sharded step contains collectives: every rank takes part in the profiled steps
         prof = kernel_profile(mapper._eager, max(3, args.profile_iters // 4))
     if rank == 0:
-        pct = step_statistics(step) if world == 1 else None        # outside the timed region
-        if prof is None:
-            prof = kernel_profile(eager_step, args.profile_iters)   # eager: the HIP events sit inside the C-ABI calls
         n = wl.R * wl.S
         out = {
             "metric": "ray.samples/s (render+bwd)", "value": value, "unit": "ray.samples/s", "n_gpus": world,
@@ -480,11 +543,15 @@ def run():
                        "launch": ("hipGraph replay of the captured iteration" + (" (one graph per step: [unpack of the previous iteration, this iteration up to its pack], the one all-reduce eager behind it)" if mapper is not None
                                                                                               else ""))
                        if graphed else "eager launches from Python"},
-            # (ray-sharded runs: this rank's kernels on this rank's shard; the PMC bytes are collected for the N = 1 workload only)
-            "roofline": roofline(prof, n, ms_step, "5000x56_lowp" if lowp else ("8192x96" if strong else "4096x64")),
-            "kernel_ms": {k: round(v, 4) for k, v in sorted(prof.items())},
-            "step_ms_percentiles": pct,
         }
+    if rank == 0 and args.full:
+        pct = step_statistics(step) if world == 1 else None        # outside the timed region
+        if prof is None:
+            prof = kernel_profile(eager_step, args.profile_iters)   # eager: the HIP events sit inside the C-ABI calls
+        # (ray-sharded runs: this rank's kernels on this rank's shard; the PMC bytes are collected for the N = 1 workload only)
+        out["roofline"] = roofline(prof, n, ms_step, "5000x56_lowp" if lowp else ("8192x96" if strong else "4096x64"))
+        out["kernel_ms"] = {k: round(v, 4) for k, v in sorted(prof.items())}
+        out["step_ms_percentiles"] = pct
         if mapper is None and not lowp and not args.no_extras:
             out.update(side_measurements(cfg, wl, dev))
         if strong and not args.no_extras:
@@ -504,7 +571,7 @@ def run():
     if world > 1:
         dist.barrier()
     line = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # reported on rank 0 at N=1 only (a host-side baseline does not change with the GPU count)
         out["cpu_baseline"] = cpu_baseline(wl) if (world == 1 and not strong and not lowp and not args.no_cpu_baseline) else None
         if out["cpu_baseline"] is not None:
@@ -515,6 +582,7 @@ def run():
                 out["cpu_baseline"]["same_port_on_this_gpu"] = g
             except Exception as e:
                 out["cpu_baseline"]["same_port_on_this_gpu"] = {"error": f"{type(e).__name__}: {e}"}
+    if rank == 0:
         line = json.dumps(out)
     if world > 1:
         dist.barrier()

@@ -427,11 +427,11 @@ def test_integration_md_ctypes_snippet_runs_as_written():
 
 
 def test_bench_line_contract():
-    """bench.py's one JSON line: the keys the driver and the judge read, a roofline whose every fraction is <= 1, and the
+    """bench.py --full's one JSON line: the keys the driver and the judge read, a roofline whose every fraction is <= 1, and the
     CPU baseline timed beside it (a short run: 3 timed steps, bounded CPU sample)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--no-extras"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--no-extras", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -451,3 +451,40 @@ def test_bench_line_contract():
         assert kern["frac"] is None or 0.0 < kern["frac"] <= 1.0, kern
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == d["unit"] and cb["sample"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run: the headline keys and none of --full's measurements; --dump-outputs writes the last timed step's
+    loss and every parameter's gradient, and two runs with the same arguments write the same arrays (to the summation order
+    of the float atomics)."""
+    import json, os, subprocess, sys
+    from myslam_amd import scene as scn
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dirs = [], []
+    for k in range(2):
+        d = str(tmp_path / f"run{k}")
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--dump-outputs", d],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, out.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+        dirs.append(d)
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "kernel_ms", "step_ms_percentiles", "cpu_baseline", "eager_ms_per_step", "forward_only"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4096 * 64 / d["ms_per_step"] * 1e3) <= 1e-6 * d["value"]
+    files = sorted(os.listdir(dirs[0]))
+    assert files == sorted(os.listdir(dirs[1]))
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in files) <= 64 * 10**6
+    shapes = [s for g in scn.make_scene("room0").plane_shapes for s in g]
+    planes = sorted(f for f in files if f.startswith("grad_planes_") or f.startswith("grad_c_planes_"))
+    assert "loss.npy" in files and len(planes) == 12 and "grad_decoders_linears_0_weight.npy" in files
+    assert sorted(tuple(np.load(os.path.join(dirs[0], f)).shape) for f in planes) == sorted(tuple(s) for s in shapes)
+    for f in files:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), f
+        assert np.abs(a).max() > 0 and hp.rel_err(a, b) <= 1e-5, f

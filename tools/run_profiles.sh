@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/${1:-r03p}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-graph --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-graph --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 find $OUT/stats -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $OUT/kernel_stats_bench_4096x64.csv
 for wl in "4096x64:room0 4096 56 8 0.0" "8192x96:scene0000 8192 88 8 0.1" "5000x56_lowp:freiburg1_desk 5000 48 8 0.1 lowp"; do
   tag=${wl%%:*}; args=${wl#*:}
@@ -39,9 +39,9 @@ for tag in ("4096x64", "8192x96", "5000x56_lowp"):
 json.dump(doc, open(os.path.join(out, "r03_traffic.json"), "w"), indent=1)
 PY
 cp $OUT/r03_traffic.json profiles/r03_traffic.json
-python3 bench.py > $OUT/bench_4096x64.json 2> $OUT/bench.err
-python3 bench.py --strong --steps 50 --warmup 10 > $OUT/bench_strong_n1.json 2> $OUT/bench_strong.err
-python3 bench.py --lowp --steps 50 --warmup 10 --no-cpu-baseline > $OUT/bench_lowp_5000x56.json 2> $OUT/bench_lowp.err
+python3 bench.py --full > $OUT/bench_4096x64.json 2> $OUT/bench.err
+python3 bench.py --full --strong --steps 50 --warmup 10 > $OUT/bench_strong_n1.json 2> $OUT/bench_strong.err
+python3 bench.py --full --lowp --steps 50 --warmup 10 --no-cpu-baseline > $OUT/bench_lowp_5000x56.json 2> $OUT/bench_lowp.err
 # host time of the eager step: Python glue / compiled glue, channels-last / NCHW planes
 ESLAM_TORCH_EXT=0 python3 tools/host_profile.py > $OUT/host_profile_python_glue.txt 2>/dev/null
 python3 tools/host_profile.py > $OUT/host_profile_compiled_glue.txt 2>/dev/null
