@@ -11,7 +11,7 @@ import threading
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# ESLAM_HIP_LIB: another build of the SAME library (A/B of compile-time kernel variants: `make variant`, tools/ab_inproc.py); never a fallback
+# ESLAM_HIP_LIB: another build of the SAME library (A/B of two builds, e.g. of two commits: tools/ab_inproc.py); never a fallback
 LIB_PATH = os.environ.get("ESLAM_HIP_LIB") or os.path.join(_HERE, "lib", "libeslam_hip.so")
 
 ABI_VERSION = 5              # ESLAM_ABI_VERSION
@@ -162,15 +162,8 @@ def stream_handle(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-_TORCH_STREAM_WAIT = os.environ.get("ESLAM_TORCH_STREAM_WAIT", "0") == "1"
-
-
 def stream_wait(device, waiter, signaler):
     """waiter / signaler: torch.cuda.Stream, or None for the caller's current stream on `device`."""
-    if _TORCH_STREAM_WAIT:          # A/B switch (ESLAM_TORCH_STREAM_WAIT=1): torch's own Stream.wait_stream
-        (torch.cuda.current_stream(device) if waiter is None else waiter).wait_stream(
-            torch.cuda.current_stream(device) if signaler is None else signaler)
-        return
     w = stream_handle(device) if waiter is None else ctypes.c_void_p(waiter.cuda_stream)
     s = stream_handle(device) if signaler is None else ctypes.c_void_p(signaler.cuda_stream)
     with on_device(device):

@@ -157,7 +157,7 @@ __device__ __forceinline__ int opaque_zero(int loop_var) {
 // instead of __shfl_* (ds_bpermute_b32 through the LDS crossbar, ~60-100 cycles a step when each step waits for the last):
 // a ray's epilogue in the forward kernel alone is 15 such reductions.  The six steps are LLVM's own lowering of a wave64
 // scan on gfx9 (row_shr 1, 2, 4, 8, then row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3).
-// All 64 lanes must be active (as for __shfl_*).  Profiling switch: -DESLAM_NO_DPP restores the __shfl_* forms.
+// All 64 lanes must be active (as for __shfl_*).
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_from(float ident, float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ident), __builtin_bit_cast(int, v), CTRL,
@@ -176,25 +176,11 @@ __device__ __forceinline__ float wave_incl_sum(float v) {
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
-#ifdef ESLAM_NO_DPP
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
-    return v;
-#else
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_incl_sum(v)), WAVE - 1));
-#endif
 }
 
 // inclusive product scan over the 64 lanes of a wave
 __device__ __forceinline__ float wave_incl_prod(float v, int lane) {
-#ifdef ESLAM_NO_DPP
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        float o = __shfl_up(v, d, WAVE);
-        if (lane >= d) v *= o;
-    }
-    return v;
-#else
     (void)lane;
     v *= dpp_from<0x111, 0xf>(1.0f, v);
     v *= dpp_from<0x112, 0xf>(1.0f, v);
@@ -203,20 +189,11 @@ __device__ __forceinline__ float wave_incl_prod(float v, int lane) {
     v *= dpp_from<0x142, 0xa>(1.0f, v);
     v *= dpp_from<0x143, 0xc>(1.0f, v);
     return v;
-#endif
 }
 
 // inclusive suffix sum (lane i gets sum over lanes >= i): row_shl steps inside the 16-lane rows, then the totals of the later
 // rows (lane 0 of a row holds its row's total) added through the scalar unit - DPP has no broadcast in this direction
 __device__ __forceinline__ float wave_incl_suffix_sum(float v, int lane) {
-#ifdef ESLAM_NO_DPP
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        float o = __shfl_down(v, d, WAVE);
-        if (lane + d < WAVE) v += o;
-    }
-    return v;
-#else
     v += dpp_from<0x101, 0xf>(0.0f, v);
     v += dpp_from<0x102, 0xf>(0.0f, v);
     v += dpp_from<0x104, 0xf>(0.0f, v);
@@ -226,25 +203,14 @@ __device__ __forceinline__ float wave_incl_suffix_sum(float v, int lane) {
     const float t3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
     const int row = lane >> 4;
     return v + (row == 0 ? t1 + (t2 + t3) : row == 1 ? t2 + t3 : row == 2 ? t3 : 0.0f);
-#endif
 }
 
 // lane i <- lane i-1 (lane 0 <- first) / lane i <- lane i+1 (lane 63 <- last); one value of a fixed lane in every lane
 __device__ __forceinline__ float wave_up1(float v, float first) {
-#ifdef ESLAM_NO_DPP
-    const float o = __shfl_up(v, 1, WAVE);
-    return (threadIdx.x & (WAVE - 1)) == 0 ? first : o;
-#else
     return dpp_from<0x138, 0xf>(first, v);          // wave_shr:1
-#endif
 }
 __device__ __forceinline__ float wave_down1(float v, float last) {
-#ifdef ESLAM_NO_DPP
-    const float o = __shfl_down(v, 1, WAVE);
-    return (threadIdx.x & (WAVE - 1)) == WAVE - 1 ? last : o;
-#else
     return dpp_from<0x130, 0xf>(last, v);           // wave_shl:1
-#endif
 }
 template <int LANE>
 __device__ __forceinline__ float wave_lane(float v) {

@@ -125,9 +125,7 @@ __device__ __forceinline__ void mlp_out_accum(const DecFrag& f, const float4_t& 
 // GATHER_PIPELINE planes are issued before the FMAs of plane p (which then wait with vmcnt(8*GATHER_PIPELINE)).  A wave is a chain of 48 dependent
 // load -> FMA steps per ray; with one plane in flight each step exposed the full L2 / Infinity-Cache latency.
 // sched_barrier keeps the compiler from hoisting further ahead (all 48 loads of a block need > 256 VGPRs).
-#ifndef GATHER_PIPELINE
 #define GATHER_PIPELINE 1
-#endif
 
 struct PlaneTaps {              // the 4 corners x 8 channels of one lane and their bilinear weights
     float4_t a00, b00, a01, b01, a10, b10, a11, b11;
@@ -230,13 +228,12 @@ __device__ __forceinline__ void gather_features_chain(const PlaneSet& planes, in
 }
 
 // store the lane's 16 features (piece q of both levels) of decoder d for point `pt` into feat_out [N,128]
-// NT: streaming (non-temporal) stores for the features a forward pass saves (134 MB at 4096 x 64, read back once, by the
+// Streaming (non-temporal) stores for the features a forward pass saves (134 MB at 4096 x 64, read back once, by the
 // backward pass): they no longer displace plane texels from the XCD's 4 MB L2 on their way out.  Measured at 4096 x 64 /
 // 8192 x 96: forward 92 -> 89 / 234 -> 218 us, and the kernels behind it gain too (decoder backward 80 -> 74 / 215 -> 204,
 // scatter 118 -> 113 / 305 -> 292).  Non-temporal LOADS of the features in the backward pass (+2 / +25 us there) and
 // non-temporal stores of the feature GRADIENTS, which three scatter workgroups re-read through L2 (+8 us in the scatter),
 // were measured and dropped (profiles/r02/n_*).
-template <bool NT = false>
 __device__ __forceinline__ void store_features(float* feat_out, int64_t pt, int d, int q, const float feat[16]) {
     float* dst = feat_out + pt * 128 + d * 64 + 4 * q;
 #pragma unroll
@@ -247,13 +244,8 @@ __device__ __forceinline__ void store_features(float* feat_out, int64_t pt, int 
             a[i] = feat[lvl * 8 + i];
             b[i] = feat[lvl * 8 + 4 + i];
         }
-        if (NT) {
-            __builtin_nontemporal_store(a, (float4_t*)(dst + lvl * 32));
-            __builtin_nontemporal_store(b, (float4_t*)(dst + lvl * 32 + 16));
-        } else {
-            *(float4_t*)(dst + lvl * 32) = a;
-            *(float4_t*)(dst + lvl * 32 + 16) = b;
-        }
+        __builtin_nontemporal_store(a, (float4_t*)(dst + lvl * 32));
+        __builtin_nontemporal_store(b, (float4_t*)(dst + lvl * 32 + 16));
     }
 }
 
@@ -263,12 +255,11 @@ __device__ __forceinline__ void store_features(float* feat_out, int64_t pt, int 
 // wave's loads and stores retire in order on one counter): with counted stores the wait names how many may stay in flight.
 typedef unsigned uint4_bits __attribute__((ext_vector_type(4)));
 #define ESLAM_OOB_OFFSET 0xFFFFFF00u
-template <bool NT = false>
 __device__ __forceinline__ void store_features_buffer(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, const float feat[16]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)          // piece j: level j >> 1, half j & 1 - the order of store_features
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_bits, (float4_t){feat[4 * j], feat[4 * j + 1], feat[4 * j + 2], feat[4 * j + 3]}),
-                                               rsrc, (int)byte_off + 64 * j, 0, NT ? 2 : 0);      // aux bit 1 = nt
+                                               rsrc, (int)byte_off + 64 * j, 0, 2);      // aux bit 1 = nt
 }
 
 // the same 16 values read back (backward pass), gather role
@@ -456,7 +447,7 @@ __device__ __forceinline__ void store_features_lp(float* feat_out, int64_t pt, i
         short8_t v;
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = f2bf(feat[lvl * 8 + i]);
-        __builtin_nontemporal_store(v, (short8_t*)(dst + lvl * 32));      // streamed, as in store_features<true>
+        __builtin_nontemporal_store(v, (short8_t*)(dst + lvl * 32));      // streamed, as in store_features
     }
 }
 

@@ -77,12 +77,6 @@ __global__ void decode_act_bwd_kernel(const float* __restrict__ raw, const float
 #define TP 20                      // row pitch (floats) of the 16x16 transpose tiles: conflict-free, 16-B aligned
 #define TPF 68                     // row pitch of the 16-point x 64-feature tile (floats)
 #define TPH 72                     // the same tile in bf16 (shorts): 144-byte rows keep the 16-byte writes aligned
-#ifndef BWD_STAMPS
-#define BWD_STAMPS 0             // profiling only: per-phase cycle counts (s_memtime) of one wave per decoder, printed at the end
-#endif
-#ifndef BWD_FBK_LDS
-#define BWD_FBK_LDS 1              // A/B switch: 0 = re-read the block's feature rows from global memory for the g_W1 contraction
-#endif
 
 struct RayBwdIn {                  // MODE >= 1: what the composite backward of a ray reads
     const float* z_vals;           // [R,S]
@@ -107,15 +101,6 @@ struct RayBwdIn {                  // MODE >= 1: what the composite backward of 
 // LOWP: the mixed-precision tile (eslam_decode_tile.h): hidden layers recomputed and every product of the backward pass on
 // bf16 MFMA (16x16x32 / 16x16x16) with float32 accumulation - 15 MFMAs of 16 cycles per 16 points and decoder instead of
 // 68 of 32 cycles; features, activations' masks, biases and all accumulators stay float32.
-#ifndef BWD_BUFSTORE
-#define BWD_BUFSTORE 1    // A/B switch: 0 = the feature-gradient rows leave through predicated global stores (round 2)
-#endif
-#ifndef BWD_TILE_AHEAD
-#define BWD_TILE_AHEAD 1  // A/B switch: 0 = a tile requests its own first block of rows (and waits for them) at its head
-#endif
-#ifndef BWD_ABLATE
-#define BWD_ABLATE 0      // profiling only (make variant VFLAGS=-DBWD_ABLATE=n): 1 no g_feat stores, 2 no weight gradients, 4 no feature loads
-#endif
 template <int MODE, bool WGRAD, bool LOWP>
 __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t dec, const float* __restrict__ feat,
                                                       const float* __restrict__ g_o, int64_t N,
@@ -124,8 +109,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     __shared__ __attribute__((aligned(16))) float wlds[2 * DEC_LDS];
     __shared__ __attribute__((aligned(16))) float tiles[4][4][16 * TP];   // per wave: gz1, gz2, h1, h2 (as [pt][j])
     __shared__ __attribute__((aligned(16))) float gtile[4][64 * 4];       // per wave: g_o of the tile [pt][o]
-    // per wave: the block's features [pt][feature] for the g_W1 contraction (BWD_FBK_LDS): float32, or bf16 at half the pitch
-    __shared__ __attribute__((aligned(16))) float ftile[(WGRAD && BWD_FBK_LDS) ? 4 : 1][(WGRAD && BWD_FBK_LDS) ? (LOWP ? 16 * TPH / 2 : 16 * TPF) : 4];
+    // per wave: the block's features [pt][feature] for the g_W1 contraction: float32, or bf16 at half the pitch
+    __shared__ __attribute__((aligned(16))) float ftile[WGRAD ? 4 : 1][WGRAD ? (LOWP ? 16 * TPH / 2 : 16 * TPF) : 4];
     if (LOWP) stage_decoder_weights_lowp(wlds, dec, threadIdx.x, blockDim.x);
     else stage_decoder_weights(wlds, dec, threadIdx.x, blockDim.x);
     __syncthreads();
@@ -174,12 +159,6 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     gW2 = gW3 = gb1 = gb2 = (float4_t){0.f, 0.f, 0.f, 0.f};
     float gb3[3] = {0.f, 0.f, 0.f};
     float gbeta_acc = 0.0f;
-#if BWD_STAMPS
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = clock64();
-#define STAMP(i) { const unsigned long long now_ = clock64(); st_acc[i] += now_ - st_last; st_last = now_; }
-#else
-#define STAMP(i)
-#endif
 
     typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t gfrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g_feat, 0, (int)((unsigned)N * 512u), 0x00020000);
@@ -192,7 +171,6 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     // the block's feature-gradient rows, gather role: four 16-byte stores per lane (both tiles: piece j at byte 64 j of the
     // decoder's half row), ALWAYS issued; N * 512 < 2^32 - 256 is checked at the launch
     auto store_rows = [&](const int64_t p0, const int b, const int nvalid, const float gf[16]) {
-        if (BWD_ABLATE & 1) return;
         const unsigned off = (16 * b + gp < nvalid) ? (unsigned)(p0 + 16 * b + gp) * 512u + (unsigned)(d * 256 + gq * 16) : 0xFFFFFF00u;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -210,7 +188,6 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             v[2] = v[3] = (float4_t){0.f, 0.f, 0.f, 0.f};
             return;
         }
-        if (BWD_ABLATE & 4) { v[0] = v[1] = v[2] = v[3] = (float4_t){0.1f, 0.2f, -0.1f, 0.3f}; return; }
         const float* fp = feat + pt * 128 + d * 64 + 4 * gq;     // piece gq = channels 4gq.., 16+4gq.. of a level
         v[0] = *(const float4_t*)(fp);
         v[1] = *(const float4_t*)(fp + 16);
@@ -219,9 +196,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     };
 #define TOUCH(x) asm volatile("" :: "v"(x))
 #define TOUCH_ROWS { TOUCH(fnext[0]); TOUCH(fnext[1]); TOUCH(fnext[2]); TOUCH(fnext[3]); }
-    // fnext: the rows of the block that comes next - of this tile, or (BWD_TILE_AHEAD) block 0 of the tile at p0_next, requested
-    // by this tile's last block in front of its stores and waited for by the CALLER (TOUCH_ROWS) before it requests anything
-    constexpr bool AHEAD = BWD_BUFSTORE && BWD_TILE_AHEAD;
+    // fnext: the rows of the block that comes next - of this tile, or block 0 of the tile at p0_next, requested by this tile's
+    // last block in front of its stores and waited for by the CALLER (TOUCH_ROWS) before it requests anything
     float4_t fnext[4];
     auto tile_bwd = [&](const int64_t p0, const int nvalid, const float go[4], const int64_t p0_next) {
         const int nblk = (nvalid + 15) >> 4;
@@ -232,7 +208,6 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
 
         // gather role: the 16 features of point 16b + gp, piece gq.  The rows of block b+1 are requested before block b is
         // computed: at 2 waves per SIMD nothing else hides the ~2k-cycle load latency.
-        if (!AHEAD) load_block(0, fnext, p0);
         // A wave's loads and stores retire in order on ONE counter (vmcnt).  A block's rows are requested a block ahead, i.e.
         // BEFORE the previous block's four feature-gradient stores, so "all but the 4 youngest operations have retired" is all
         // the top of a block has to wait for - but the compiler can only say so if it can COUNT the stores: as predicated
@@ -240,8 +215,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
         // ray's first use of its prefetched inputs - sat out the store acknowledgement of the block before (~2 k and ~5 k
         // cycles: 45 % of a ray's ~30 k, profiles/r02/t_*).  The stores are therefore buffer stores that are ALWAYS issued - rows
         // past the end get an offset beyond the descriptor's range, which the hardware drops - and four such dropped stores
-        // behind the first block's loads give the loop's entry the same shape as its back edge.
-        if (BWD_BUFSTORE && !AHEAD) dropped_stores();
+        // behind the first block's loads (issued by the caller) give the loop's entry the same shape as its back edge.
 #pragma unroll 1
         for (int b = 0; b < nblk; ++b) {
             float ft[16];
@@ -251,34 +225,23 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             }
             // (two blocks ahead: 250 VGPRs, no faster.)  ONE request site with a selected address: two sites behind an if / else
             // made the compiler wait for vmcnt(0)
-            if (AHEAD) load_block(0, fnext, b + 1 < nblk ? p0 + 16 * (b + 1) : p0_next);
-            else if (b + 1 < nblk) load_block(b + 1, fnext, p0);
-            // the same rows again in the "feature on the lane" layout of the g_W1 contraction (B operand): requested
-            // here so that the L1/L2 latency is covered by the 28 MFMAs of the recompute instead of stalling them later
-            // float32 path: NOT re-read from memory but handed over through a wave-private LDS tile, written here in the
-            // gather role and read back just before the contraction.  The global re-read (L1 / L2 hits) was waited for in the
-            // middle of the block - behind the previous block's four feature-gradient stores, a wave's loads and stores
-            // retiring in order - which exposed those stores' latency in every block (15 us of this kernel at 4096 x 64).
-            constexpr bool FBK_LDS = WGRAD && BWD_FBK_LDS != 0;
+            load_block(0, fnext, b + 1 < nblk ? p0 + 16 * (b + 1) : p0_next);
+            // the same rows again in the "feature on the lane" layout of the g_W1 contraction (B operand): NOT re-read from
+            // memory but handed over through a wave-private LDS tile, written here in the gather role and read back just before
+            // the contraction.  A global re-read (L1 / L2 hits) was waited for in the middle of the block - behind the previous
+            // block's four feature-gradient stores, a wave's loads and stores retiring in order - which exposed those stores'
+            // latency in every block (15 us of this kernel at 4096 x 64).
             float4_t fbk[4];
             short4_t fbkp[4];
-            if (FBK_LDS && LOWP) {          // bf16: the lane holds channels 8gq..8gq+7 of each level as 4 + 4 floats' worth of bits
+            if (WGRAD && LOWP) {          // bf16: the lane holds channels 8gq..8gq+7 of each level as 4 + 4 floats' worth of bits
                 short* T = (short*)ftile[wave] + gp * TPH + 8 * gq;
                 *(float4_t*)(T) = (float4_t){ft[0], ft[1], ft[2], ft[3]};
                 *(float4_t*)(T + 32) = (float4_t){ft[4], ft[5], ft[6], ft[7]};
-            } else if (FBK_LDS) {
+            } else if (WGRAD) {
                 float* T = ftile[wave] + gp * TPF + 4 * gq;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) *(float4_t*)(T + 16 * j) = (float4_t){ft[4 * j], ft[4 * j + 1], ft[4 * j + 2], ft[4 * j + 3]};
-            } else if (WGRAD) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int64_t pk = min(p0 + 16 * b + 4 * q + ks, N - 1);
-                    if (LOWP) fbkp[ks] = *(const short4_t*)((const short*)feat + pk * 128 + d * 64 + 4 * r);
-                    else fbk[ks] = (BWD_ABLATE & 4) ? (float4_t){0.1f, 0.2f, 0.3f, 0.4f} : *(const float4_t*)(feat + pk * 128 + d * 64 + 4 * r);
-                }
             }
-            STAMP(1)
             if (LOWP) to_mfma_role<true, 8>(ft, lane);       // 8 registers of packed bf16 pairs
             else to_mfma_role<true, 16>(ft, lane);
             float4_t h1, h2, gz1, gz2;
@@ -318,16 +281,9 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                     for (int i = 0; i < 4; ++i) gf[4 * mb + i] = acc[i];
                 }
                 to_gather_role<true, 16>(gf, lane);
-                if (BWD_BUFSTORE) store_rows(p0, b, nvalid, gf);
-                else if (p0 + 16 * b + gp < p0 + nvalid) {       // gather-role lane (point, g): features 16 mb + 4 g + i
-                    float* dst = g_feat + (p0 + 16 * b + gp) * 128 + d * 64 + 4 * gq;
-#pragma unroll
-                    for (int mb = 0; mb < 4; ++mb)
-                        *(float4_t*)(dst + 16 * mb) = (float4_t){gf[4 * mb], gf[4 * mb + 1], gf[4 * mb + 2], gf[4 * mb + 3]};
-                }
+                store_rows(p0, b, nvalid, gf);
             } else {
             mlp_hidden(f, ft, h1, h2);
-            STAMP(2)
 
             // g_h2^T = W3^T . g_o^T   (K = (block', o); only block' == b contributes)
             float4_t gh2 = (float4_t){0.f, 0.f, 0.f, 0.f};
@@ -354,13 +310,10 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) gf[(mb >> 1) * 8 + 4 * (mb & 1) + i] = acc[i];
             }
-            STAMP(3)
             to_gather_role<true, 16>(gf, lane);
-            if (BWD_BUFSTORE) store_rows(p0, b, nvalid, gf);
-            else if (!(BWD_ABLATE & 1) && p0 + 16 * b + gp < p0 + nvalid) store_features(g_feat, p0 + 16 * b + gp, d, gq, gf);
+            store_rows(p0, b, nvalid, gf);
             }
-            STAMP(4)
-            if (!WGRAD || (BWD_ABLATE & 2)) continue;
+            if (!WGRAD) continue;
 
             // transposes through LDS: D layout (rows 4q+reg, col = point r) -> [point][row]
             *(float4_t*)(tz1 + r * TP + 4 * q) = gz1;
@@ -380,17 +333,14 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 bh2[ks] = th2[prow * TP + r];
                 ago[ks] = (r < 4) ? gt[(16 * b + prow) * 4 + r] : 0.0f;
             }
-            STAMP(5)
             if (LOWP) {      // the same contractions over the block's 16 points, K = 16 in one bf16 MFMA each
                 gW2 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pack4(az2[0], az2[1], az2[2], az2[3]),
                                                                 pack4(bh1[0], bh1[1], bh1[2], bh1[3]), gW2, 0, 0, 0);
                 gW3 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pack4(ago[0], ago[1], ago[2], ago[3]),
                                                                 pack4(bh2[0], bh2[1], bh2[2], bh2[3]), gW3, 0, 0, 0);
                 const short4_t a1p = pack4(az1[0], az1[1], az1[2], az1[3]);
-                if (FBK_LDS) {
 #pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) fbkp[ks] = *(const short4_t*)((const short*)ftile[wave] + (4 * q + ks) * TPH + 4 * r);
-                }
+                for (int ks = 0; ks < 4; ++ks) fbkp[ks] = *(const short4_t*)((const short*)ftile[wave] + (4 * q + ks) * TPH + 4 * r);
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb)
                     gW1[nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a1p, (short4_t){fbkp[0][nb], fbkp[1][nb], fbkp[2][nb], fbkp[3][nb]},
@@ -402,10 +352,9 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 gW3 = mfma16(ago[ks], bh2[ks], gW3);              // g_W3[o][j]  : rows o = 4q+reg (q = 0), col j = r
             }
             // g_W1[j][f]: B = features of point 4q+ks, columns permuted: column c of n-block nb <-> feature 4c + nb
-            if (FBK_LDS) {      // (the tile was written before this block's first WAVE_SYNC)
+            // (the tile was written before this block's first WAVE_SYNC)
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fbk[ks] = *(const float4_t*)(ftile[wave] + (4 * q + ks) * TPF + 4 * r);
-            }
+            for (int ks = 0; ks < 4; ++ks) fbk[ks] = *(const float4_t*)(ftile[wave] + (4 * q + ks) * TPF + 4 * r);
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
@@ -413,14 +362,13 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             }
             }
             WAVE_SYNC();
-            STAMP(6)
         }
     };
 
     if (MODE == 0) {
         const int64_t ntiles = (N + 63) / 64;
         int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-        if (AHEAD && tile < ntiles) {
+        if (tile < ntiles) {
             load_block(0, fnext, tile * 64);
             dropped_stores();
         }
@@ -434,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 if (d == 0) go[0] = g[3];
                 else { go[0] = g[0]; go[1] = g[1]; go[2] = g[2]; }
             }
-            if (AHEAD) TOUCH_ROWS
+            TOUCH_ROWS
             tile_bwd(p0, nvalid, go, (tile + (int64_t)gridDim.x * 4) * 64);
         }
     } else {
@@ -508,10 +456,9 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             rin = load_ray(ray);
             cin = load_chunk(ray, nchunk - 1);
             pin = load_pa(ray);
-            if (AHEAD) load_block(0, fnext, (int64_t)ray * S + (nchunk - 1) * WAVE);
+            load_block(0, fnext, (int64_t)ray * S + (nchunk - 1) * WAVE);
         }
-        constexpr bool COUNTED = BWD_BUFSTORE != 0;           // the waits below are counted by the compiler: see tile_bwd
-        if (COUNTED) dropped_stores();
+        dropped_stores();                                     // the waits below are counted by the compiler: see tile_bwd
 #define TOUCH_CHUNK(ci) { TOUCH(ci.sd); TOUCH(ci.z); TOUCH(ci.cr); TOUCH(ci.cg); TOUCH(ci.cb); TOUCH(ci.gs); }
         for (; ray < R; ray += stride) {
             const int64_t base = (int64_t)ray * S;
@@ -520,13 +467,11 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             // (Waited for at its first use further down, the wait would cover the requests issued meanwhile as well - the
             // compiler cannot count those: optional pointers, rows past S - and expose their whole latency in every ray:
             // 5.5 k cycles of a ray's ~30 k, profiles/r02/t_*.)
-            if (COUNTED) {
-                TOUCH(rin.gd); TOUCH(rin.gr); TOUCH(rin.gg); TOUCH(rin.gb); TOUCH(rin.gtd); TOUCH(rin.dep); TOUCH(rin.cr); TOUCH(rin.cg);
-                TOUCH(rin.cb); TOUCH(rin.tr); TOUCH(rin.tg); TOUCH(rin.tb); TOUCH(rin.mask);
-                TOUCH_CHUNK(cin)
-                TOUCH(pin.sd[0]); TOUCH(pin.sd[1]); TOUCH(pin.sd[2]);
-                if (AHEAD) TOUCH_ROWS
-            }
+            TOUCH(rin.gd); TOUCH(rin.gr); TOUCH(rin.gg); TOUCH(rin.gb); TOUCH(rin.gtd); TOUCH(rin.dep); TOUCH(rin.cr); TOUCH(rin.cg);
+            TOUCH(rin.cb); TOUCH(rin.tr); TOUCH(rin.tg); TOUCH(rin.tb); TOUCH(rin.mask);
+            TOUCH_CHUNK(cin)
+            TOUCH(pin.sd[0]); TOUCH(pin.sd[1]); TOUCH(pin.sd[2]);
+            TOUCH_ROWS
             ChunkIn ch = cin;
             RayIn rnx = {};
             ChunkIn cnx = {};
@@ -569,19 +514,17 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 const bool valid = c * WAVE + lane < S;
                 float gs = ch.gs;
                 if (MODE == 2 && valid) gs += loss_g_sdf(m, ch.z, ch.sd, gtd, li.tr, lk);
-                STAMP(7)
                 const float4_t o = composite_bwd_chunk(up, beta, valid, ch.sd, ch.z, ch.cr, ch.cg, ch.cb, gs, trans_in, carry,
                                                        gbeta_acc, lane);
                 float go[4] = {0.f, 0.f, 0.f, 0.f};
                 if (d == 0) go[0] = o[3];
                 else { go[0] = o[0]; go[1] = o[1]; go[2] = o[2]; }
-                STAMP(0)
                 // the tile after this one: the chunk in front of it, or the last chunk of the wave's next ray (rows past N are clamped)
                 tile_bwd(base + c * WAVE, min(WAVE, S - c * WAVE), go,
                          c > 0 ? base + (c - 1) * WAVE : (int64_t)(ray + stride) * S + (nchunk - 1) * WAVE);
                 if (c > 0) {
-                    if (COUNTED) TOUCH_CHUNK(cn)
-                    if (AHEAD) TOUCH_ROWS
+                    TOUCH_CHUNK(cn)
+                    TOUCH_ROWS
                     ch = cn;
                 }
             } while (--c >= 0);
@@ -600,12 +543,6 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             rb.beta_parts[blockIdx.x] = (beta_part[0] + beta_part[1]) + (beta_part[2] + beta_part[3]);
     }
 
-#if BWD_STAMPS
-    if (blockIdx.x == 5 && threadIdx.x == 0)
-        printf("stamps d=%d cycles: composite %llu | top of a block (wait for its feature rows) %llu | recompute issue %llu | backward mfma issue %llu | "
-               "role change + stores (waits for the MFMA chain) %llu | lds transposes %llu | weight gradients %llu | ray prologue %llu\n",
-               d, st_acc[0], st_acc[1], st_acc[2], st_acc[3], st_acc[4], st_acc[5], st_acc[6], st_acc[7]);
-#endif
     if (!WGRAD) return;
     // the four waves' partial parameter gradients are summed in LDS; one slab row per workgroup: [wg][decoder][SLAB]
     __shared__ __attribute__((aligned(16))) float comb[4][SLAB];

@@ -25,24 +25,11 @@ struct LossIn {
     int det;               // ESLAM_DETERMINISTIC: fixed-order reduction of the workgroups' sums
 };
 
-// LOWP: the mixed-precision tile of eslam_decode_tile.h (fp16 plane copies, bf16 MFMA decoders); channels-last only.
-template <bool CL, bool SAVE, bool LOSS, bool LOWP>
-#ifndef FWD_FEAT_NT
-#define FWD_FEAT_NT 1            // A/B switches (make variant VFLAGS=-DFWD_FEAT_NT=0 / -DFWD_CHAIN=0)
-#endif
-#ifndef FWD_CHAIN
-#define FWD_CHAIN 1
-#endif
-#ifndef FWD_Z_PERMUTE
-#define FWD_Z_PERMUTE 1        // a block's z values by lane permute from one load per chunk (0: one dependent load per block)
-#endif
-#ifndef FWD_BUFSTORE
-#define FWD_BUFSTORE 1         // the saved features leave through always-issued buffer stores (countable: store_features_buffer)
-#endif
-#ifndef FWD_WAVES
 #define FWD_WAVES 2            // waves per SIMD the gather kernels are compiled for: with one plane of loads in flight
                                // ahead of the FMAs the forward kernel needs 195 VGPRs; 2 waves/SIMD measured fastest
-#endif
+
+// LOWP: the mixed-precision tile of eslam_decode_tile.h (fp16 plane copies, bf16 MFMA decoders); channels-last only.
+template <bool CL, bool SAVE, bool LOSS, bool LOWP>
 __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneSet planes, const eslam_decoders_t dec,
                                                          const Bound bnd, const float* __restrict__ rays_o,
                                                          const float* __restrict__ rays_d,
@@ -104,12 +91,12 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
         // permute - as a load per block the value sat on the critical path of the NEXT block's first texel request
         const float zs = zrow[min(c0 + lane, S - 1)];
         auto block_point = [&](int b, float& px, float& py, float& pz) {
-            const float zb = FWD_Z_PERMUTE ? __shfl(zs, 16 * b + gp, WAVE) : zrow[min(c0 + 16 * b + gp, S - 1)];
+            const float zb = __shfl(zs, 16 * b + gp, WAVE);
             px = norm_coord(ox + dx * zb, bnd.lo[0], bnd.hi[0]);
             py = norm_coord(oy + dy * zb, bnd.lo[1], bnd.hi[1]);
             pz = norm_coord(oz + dz * zb, bnd.lo[2], bnd.hi[2]);
         };
-        constexpr bool CHAIN = CL && !LOWP && FWD_CHAIN != 0;    // float32 channels-last planes: texel requests run one block ahead
+        constexpr bool CHAIN = CL && !LOWP;    // float32 channels-last planes: texel requests run one block ahead
         PlaneTaps carry;
         float cx = 0.f, cy = 0.f, cz = 0.f;
         if (CHAIN) {
@@ -131,12 +118,11 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
                     gather_features_chain(planes, d, cx, cy, cz, gq, feat, oz0, carry, last ? 1 : d, nx, ny, nz);
                     cx = nx; cy = ny; cz = nz;
                     if (SAVE) {
-                        if (FWD_BUFSTORE) {
-                            __builtin_amdgcn_sched_barrier(0);      // (left alone, the scheduler sinks the stores behind the MLP)
-                            store_features_buffer<FWD_FEAT_NT != 0>(frsrc, sb < S ? (unsigned)(ray * S + sb) * 512u + (unsigned)(d * 256 + gq * 16)
-                                                                                  : ESLAM_OOB_OFFSET, feat);
-                            __builtin_amdgcn_sched_barrier(0);
-                        } else if (sb < S) store_features<FWD_FEAT_NT != 0>(feat_out, (int64_t)ray * S + sb, d, gq, feat);
+                        // the saved features leave through always-issued buffer stores (countable: store_features_buffer)
+                        __builtin_amdgcn_sched_barrier(0);      // (left alone, the scheduler sinks the stores behind the MLP)
+                        store_features_buffer(frsrc, sb < S ? (unsigned)(ray * S + sb) * 512u + (unsigned)(d * 256 + gq * 16)
+                                                            : ESLAM_OOB_OFFSET, feat);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                     to_mfma_role<CL, 16>(feat, lane);
                     DecFrag f;
@@ -163,7 +149,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
                 }
                 gather_features<CL>(planes, d, px, py, pz, gq, feat, oz0);
                 if (SAVE) {
-                    if (sb < S) store_features<FWD_FEAT_NT != 0>(feat_out, (int64_t)ray * S + sb, d, gq, feat);
+                    if (sb < S) store_features(feat_out, (int64_t)ray * S + sb, d, gq, feat);
                 }
                 to_mfma_role<CL, 16>(feat, lane);
                 // operand fragments are re-read from LDS per block (9 ds_read_b128) instead of being kept live across
@@ -179,7 +165,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
         // ---- sample role: activations, alpha, transmittance scan, composite (Renderer.py:140-153) ----
         const bool valid = lane < nvalid;
         const int s = c0 + lane;
-        const float z = valid ? (FWD_Z_PERMUTE ? zs : zrow[s]) : 0.0f;
+        const float z = valid ? zs : 0.0f;
         const float sdf = tanhf(out[0][0]);
         const float cr = sigmoidf_(out[1][0]), cg = sigmoidf_(out[1][1]), cb = sigmoidf_(out[1][2]);
         if (valid) {
@@ -277,7 +263,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneS
                 float feat[16];
                 gather_features<CL>(planes, d, px, py, pz, gq, feat, oz0);
                 if (SAVE) {
-                    if (pb < N) store_features<FWD_FEAT_NT != 0>(feat_out, pb, d, gq, feat);
+                    if (pb < N) store_features(feat_out, pb, d, gq, feat);
                 }
                 to_mfma_role<CL, 16>(feat, lane);
                 DecFrag f;
@@ -356,8 +342,7 @@ static int render_fwd_common(const char* who, const eslam_plane_t* planes, const
     static const int resident = [] {        // workgroups the chip holds at once: FWD_WAVES waves per SIMD = FWD_WAVES workgroups per CU
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        static const char* e = getenv("ESLAM_FWD_PERSIST");
-        return (e && e[0] == '0') ? (1 << 30) : ((FWD_WAVES * cus) / 8) * 8;
+        return ((FWD_WAVES * cus) / 8) * 8;
     }();
     // persistent only when the rays divide evenly over the resident workgroups (4096, 8192 rays ...): a static assignment of
     // 2.44 rays per wave (5000 rays) runs three rounds where the hardware's own dispatch of 1250 workgroups needs 2.5

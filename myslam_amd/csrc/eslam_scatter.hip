@@ -19,7 +19,6 @@
 //                     (bitonic network), (3) gives each wave a contiguous quarter of the sorted list to walk with
 //                     lane = (x-corner, channel): consecutive entries of one cell are summed in two registers (rows
 //                     y0, y1) and each cell is written once with two 256-B-shaped float atomics.
-#include <stdlib.h>
 #include <mutex>
 #include <type_traits>
 #include "eslam_decode_tile.h"
@@ -48,26 +47,22 @@ __device__ __forceinline__ unsigned spread3(unsigned v) {      // 10 bits -> eve
 // network in one workgroup took 62 us).
 // When all rays of the chunk leave from ONE point (a tracking batch; a mapping batch of a single frame) their
 // directions form a 2-D patch, and a 3-D Morton code wastes a third of its bits on a coordinate the other two
-// determine: the key is then the 16-bit Hilbert index of the direction's gnomonic projection about the mean
-// direction - neighbours along the curve are always neighbours in the image.  Measured on the bench workload:
-// 14 % fewer cell flushes, scatter 124 -> 116 us (tools/sim_order.py, tools/exp_order.py).
-#ifndef RAY_ORDER_AZIMUTH
-#define RAY_ORDER_AZIMUTH 1       // A/B switch: 0 = the three orders are the same 2-D Hilbert order (round 2)
-#endif
+// determine: the key is then the azimuth of the direction projected into the order's plane (see below).  Round 2's
+// 16-bit Hilbert index of the direction's gnomonic projection, one order for all planes, had measured 14 % fewer cell
+// flushes than the Morton code on the bench workload (scatter 124 -> 116 us; tools/sim_order.py, tools/exp_order.py).
 #define ORD_BITS 5
 #define ORD_CELLS (1 << (3 * ORD_BITS))      // 32768 words = 65536 packed 16-bit counters = 128 KB of LDS
 #define ORD_PER_THREAD (SORT_MAX / 1024)
-// key_bits (12, 14 or 16): keys of the counting sort.  The histogram's zero fill and scan are what this single-workgroup
-// kernel spends its time on, so small batches get short keys (12 bits for <= 1024 rays: 2048 words instead of 32768).
+// key_bits (12 or 14): keys of the counting sort.  The histogram's zero fill and scan are what this single-workgroup
+// kernel spends its time on, so small batches get short keys (12 bits for <= 1024 rays: 2048 words instead of 8192).
 __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict__ rays_o,
                                                          const float* __restrict__ rays_d, int R,
-                                                         int* __restrict__ perm, int key_bits, int max_cams) {
+                                                         int* __restrict__ perm, int key_bits) {
     extern __shared__ __attribute__((aligned(16))) unsigned hist[];       // [(1 << key_bits) / 2] packed 16-bit counters
     const int nwords = (1 << key_bits) >> 1;
-    const int hbits = key_bits >> 1;                                      // Hilbert grid: 2^hbits x 2^hbits
     const int mbits = key_bits / 3;                                       // Morton grid: 2^mbits per axis
     __shared__ float red[16][6];
-    __shared__ float red2[16][13];
+    __shared__ float red2[16][11];
     __shared__ unsigned wsum[16];
     // several origins (a keyframe window, src/Mapper.py:308-319: the batch is camera-major): which rays start a new camera
     // (bit i of the map: ray i leaves from another point than ray i - 1), the running count per 64 rays, and per camera the sum
@@ -86,7 +81,7 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
     // blockIdx.y = plane orientation (0: xy, 1: xz, 2: yz): order number o is written to perm + o * R.  When the rays share one
     // origin, order o sorts them by the AZIMUTH of their direction projected into plane o: the rays of a bundle then lie on top
     // of each other in that plane's projection whatever their angle out of it, and that is what shares cells - a plane collapses
-    // one axis, so a square patch of the image (the Hilbert order: one order for all planes) spreads over many more cells of
+    // one axis, so a square patch of the image (round 2's Hilbert order: one order for all planes) spreads over many more cells of
     // each plane than a thin wedge does.  tools/sim_order.py, bench rays: 58.8 k cell flushes against 135 k.
     const int orient = blockIdx.y;
     float* const fan = (float*)(perm + (size_t)ESLAM_RAY_ORDERS * R);      // [ESLAM_RAY_ORDERS] angular extent of the fan in each plane (0: unknown)
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
     const int pa = orient == 2 ? 1 : 0, pb = orient == 0 ? 1 : 2;       // the plane's two axes
 
     // Rays are re-read from memory (98 KB, cache resident) in every pass instead of being held in 24 registers per
-    // thread: at 1024 threads per workgroup the budget is 128 VGPRs, and the Hilbert path spilled.
+    // thread: at 1024 threads per workgroup the budget is 128 VGPRs, and round 2's Hilbert path spilled.
     auto unit_dir = [&](int ray, float o[3], float d[3]) {
         const float dx = rays_d[3 * ray], dy = rays_d[3 * ray + 1], dz = rays_d[3 * ray + 2];
         const float inv = rsqrtf(fmaxf(dx * dx + dy * dy + dz * dz, 1e-20f));
@@ -155,8 +150,8 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
     };
     auto sortable = [](float x) { const unsigned u = __float_as_uint(x); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
     auto unsortable = [](unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); };
-    const bool per_camera = RAY_ORDER_AZIMUTH && ncam >= 2 && ncam <= min(NCAM_MAX, max_cams);
-    // one origin?  then order by the Hilbert index of the direction in a 2-D chart about the mean direction
+    const bool per_camera = ncam >= 2 && ncam <= NCAM_MAX;
+    // one origin?  then order by the azimuth of the direction about the mean direction
     float mdir[3];
     bool single = true;
 #pragma unroll
@@ -215,77 +210,38 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
             __builtin_amdgcn_sched_barrier(0);
         }
     } else if (single) {                                // uniform over the workgroup
-        const float m0 = mdir[0] / mlen, m1 = mdir[1] / mlen, m2 = mdir[2] / mlen;
-        // e1 = normalize(m x axis least aligned with m), e2 = m x e1
-        float ax0 = 1.f, ax1 = 0.f, ax2 = 0.f;
-        if (fabsf(m1) <= fabsf(m0) && fabsf(m1) <= fabsf(m2)) { ax0 = 0.f; ax1 = 1.f; }
-        else if (fabsf(m2) <= fabsf(m0) && fabsf(m2) <= fabsf(m1)) { ax0 = 0.f; ax2 = 1.f; }
-        float e10 = m1 * ax2 - m2 * ax1, e11 = m2 * ax0 - m0 * ax2, e12 = m0 * ax1 - m1 * ax0;
-        const float el = rsqrtf(e10 * e10 + e11 * e11 + e12 * e12);
-        e10 *= el; e11 *= el; e12 *= el;
-        const float e20 = m1 * e12 - m2 * e11, e21 = m2 * e10 - m0 * e12, e22 = m0 * e11 - m1 * e10;
-        const float mm[3] = {m0, m1, m2};
-        const float mpa = mm[pa], mpb = mm[pb];           // the mean direction projected into the plane
-        auto chart = [&](int ray, float& u, float& v) {
+        const float mpa = mdir[pa] / mlen, mpb = mdir[pb] / mlen;      // the mean direction projected into the plane
+        // the signed angle between the projected direction and the projected mean
+        auto azimuth = [&](int ray) {
             float o[3], d[3];
             unit_dir(ray, o, d);
-            if (RAY_ORDER_AZIMUTH) {                     // u = signed angle between the projected direction and the projected mean
-                u = atan2f(mpa * d[pb] - mpb * d[pa], mpa * d[pa] + mpb * d[pb]);
-                v = 0.0f;
-                return;
-            }
-            // gnomonic chart about the mean direction, clamped at ~87 degrees
-            const float t = fmaxf(d[0] * m0 + d[1] * m1 + d[2] * m2, 0.05f);
-            u = (d[0] * e10 + d[1] * e11 + d[2] * e12) / t;
-            v = (d[0] * e20 + d[1] * e21 + d[2] * e22) / t;
+            return atan2f(mpa * d[pb] - mpb * d[pa], mpa * d[pa] + mpb * d[pb]);
         };
-        float blo[2] = {3.4e38f, 3.4e38f}, bhi[2] = {-3.4e38f, -3.4e38f};
+        float blo = 3.4e38f, bhi = -3.4e38f;
         for (int i = tid; i < n; i += 1024) {
-            float u, v;
-            chart(base + i, u, v);
-            blo[0] = fminf(blo[0], u); bhi[0] = fmaxf(bhi[0], u);
-            blo[1] = fminf(blo[1], v); bhi[1] = fmaxf(bhi[1], v);
+            const float u = azimuth(base + i);
+            blo = fminf(blo, u); bhi = fmaxf(bhi, u);
         }
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                blo[a] = fminf(blo[a], __shfl_xor(blo[a], m, WAVE));
-                bhi[a] = fmaxf(bhi[a], __shfl_xor(bhi[a], m, WAVE));
-            }
-            if (lane == 0) { red2[wave][9 + a] = blo[a]; red2[wave][11 + a] = bhi[a]; }
+        for (int m = 32; m >= 1; m >>= 1) {
+            blo = fminf(blo, __shfl_xor(blo, m, WAVE));
+            bhi = fmaxf(bhi, __shfl_xor(bhi, m, WAVE));
         }
+        if (lane == 0) { red2[wave][9] = blo; red2[wave][10] = bhi; }
         __syncthreads();
-        float sc2[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            float l = red2[0][9 + a], h = red2[0][11 + a];
-            for (int w = 1; w < 16; ++w) { l = fminf(l, red2[w][9 + a]); h = fmaxf(h, red2[w][11 + a]); }
-            blo[a] = l;
-            sc2[a] = (float)(1 << (RAY_ORDER_AZIMUTH ? key_bits : hbits)) / fmaxf(h - l, 1e-6f);
-            // the fan's angular extent in this plane (radians), for the scatter's choice of grid order; the first chunk speaks for the batch
-            if (a == 0 && tid == 0 && blockIdx.x == 0) fan[orient] = RAY_ORDER_AZIMUTH ? h - l : 0.0f;
-        }
+        float h = red2[0][10];
+        blo = red2[0][9];
+        for (int w = 1; w < 16; ++w) { blo = fminf(blo, red2[w][9]); h = fmaxf(h, red2[w][10]); }
+        const float sc = (float)(1 << key_bits) / fmaxf(h - blo, 1e-6f);
+        // the fan's angular extent in this plane (radians), for the scatter's choice of grid order; the first chunk speaks for the batch
+        if (tid == 0 && blockIdx.x == 0) fan[orient] = h - blo;
 #pragma unroll
         for (int k = 0; k < ORD_PER_THREAD; ++k) {
             const int i = tid + k * 1024;
             if (i < n) {
-                float u, v;
-                chart(base + i, u, v);
-                const unsigned hmax = (1u << (RAY_ORDER_AZIMUTH ? key_bits : hbits)) - 1u;
-                unsigned x = min((unsigned)fmaxf((u - blo[0]) * sc2[0], 0.f), hmax);
-                unsigned y = min((unsigned)fmaxf((v - blo[1]) * sc2[1], 0.f), hmax);
-                unsigned d = RAY_ORDER_AZIMUTH ? x : 0u; // azimuth: the quantised angle is the key; else the Hilbert index of (x, y)
-                for (unsigned sft = RAY_ORDER_AZIMUTH ? 0u : 1u << (hbits - 1); sft > 0; sft >>= 1) {
-                    const unsigned rx = (x & sft) ? 1u : 0u, ry = (y & sft) ? 1u : 0u;
-                    d += sft * sft * ((3u * rx) ^ ry);
-                    if (ry == 0) {
-                        if (rx == 1) { x = hmax - x; y = hmax - y; }
-                        const unsigned tswap = x; x = y; y = tswap;
-                    }
-                }
-                key[k] = d;
-                ticket[k] = (atomicAdd(&hist[d >> 1], 1u << ((d & 1u) * 16u)) >> ((d & 1u) * 16u)) & 0xFFFFu;
+                const unsigned kk = min((unsigned)fmaxf((azimuth(base + i) - blo) * sc, 0.f), (1u << key_bits) - 1u);
+                key[k] = kk;
+                ticket[k] = (atomicAdd(&hist[kk >> 1], 1u << ((kk & 1u) * 16u)) >> ((kk & 1u) * 16u)) & 0xFFFFu;
             }
             __builtin_amdgcn_sched_barrier(0);           // one ray at a time keeps the register pressure down
         }
@@ -355,15 +311,9 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------------------
 // bundle scatter
 // ---------------------------------------------------------------------------------------------------------
-// NT threads per workgroup, BM = 4*NT samples per workgroup (power of two).
-//   DBG: 0 production; 1 walk without atomics; 2 stop after the sort; 3 = 1 without the g_feat row loads; 4 = 3 without the
-//   LDS weight reads; 5 = 3 WITH the atomics (atomics, but no loads queued behind them); 6 = 0 with plain stores in place of
-//   the atomics (profiling only, tools/scatter_anatomy.sh; 5 and 6 write garbage into the gradients)
+// NT = 512 threads per workgroup, BM = SPT*NT samples per workgroup (power of two).
 //   (Round 2 had the kernel's two halves - cells + sort / walk - as separately launchable phases, the first one beside the
 //   forward kernel on a side stream: 0.369 vs 0.323 ms per step, DESIGN.md section 10.  Removed in round 3.)
-#ifndef SC_STAMPS
-#define SC_STAMPS 0                                   // profiling only: per-phase cycles of one workgroup's first thread
-#endif
 //   DET (ESLAM_DETERMINISTIC=1): the sums of a cell are formed in 64-bit fixed point (2^-44 units: integer adds commute, so
 //   neither the arbitrary order of the counting sort's tickets inside a cell, nor the order in which workgroups' atomics
 //   reach a texel, nor the ray order itself can change a bit of the result) and added to an int64 shadow of the gradient
@@ -372,17 +322,17 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
 #define FIX_LIMIT 262144.0f                          // |one contribution| < 2^18: 2^62 in fixed point; a texel's SUM wraps beyond
                                                      // 2^63 / 2^44 = 5.2e5 - contributions past the limit poison the gradient (NaN)
 struct ShadowOff { int64_t o[NPL]; };
-template <bool RENDER, int DBG, int NT, bool DET, int SPT = 4>
-__global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes, const Bound bnd,
+constexpr int SC_NT = 512;
+template <bool RENDER, bool DET, int SPT = 4>
+__global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet planes, const Bound bnd,
                                                           const float* __restrict__ rays_o,
                                                           const float* __restrict__ rays_d,
                                                           const float* __restrict__ z_vals,     // RENDER ? [R,S] : pts [N,3]
                                                           const int* __restrict__ perm, int R, int S,
-                                                          const float* __restrict__ g_feat, int bundle,
-                                                          int allow_counting, int nbundles, int xcd_map,
+                                                          const float* __restrict__ g_feat, int bundle, int nbundles,
                                                           long long* __restrict__ shadow,
                                                           const ShadowOff shoff, const DecReduceArgs red, const int red_blocks) {
-    constexpr int dbg_mode = DBG;
+    constexpr int NT = SC_NT;
     constexpr int BM = SPT * NT;                       // SPT samples per thread in the cell / sort phases
     constexpr int CH = WAVE * SPT;                     // sorted entries a wave walks
     static_assert(SPT == 2 || SPT == 4, "samples per thread");
@@ -422,48 +372,32 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
         return;
     }
     const int bid = (int)blockIdx.x - red_blocks;
-    int bidx, pi;
-    // Workgroup -> (bundle, plane), 1-D grid (ESLAM_SC_XCDMAP; measured in profiles/r03/l_*, one ray order per orientation):
-    //   4 (default) bundle-major: the 12 planes of bundle 0, then of bundle 1, ...  The four planes of an orientation bundle the
-    //     same rays and read the four 128-byte segments of the same feature-gradient rows close together in time.
-    //   1 round 2's dealing: the three orientations of one (bundle, decoder, level) as neighbours on ONE XCD - they read the SAME
+    // Workgroup -> (bundle, plane), 1-D grid, chosen on the device: plane-major for a WIDE fan of rays from one origin,
+    // bundle-major otherwise.  Measured (profiles/r03/l_*, one ray order per orientation; the parent of the commit that removed
+    // the other layouts reproduces them):
+    //   bundle-major: the 12 planes of bundle 0, then of bundle 1, ...  The four planes of an orientation bundle the same rays
+    //     and read the four 128-byte segments of the same feature-gradient rows close together in time.
+    //   round 2's dealing: the three orientations of one (bundle, decoder, level) as neighbours on ONE XCD - they read the SAME
     //     segment of the same rows while all planes shared one ray order (81 % of the row reads missed L2 without it); with an
-    //     order per orientation they no longer share rays, and the dealing is 0-10 us slower than 4.
-    //   3 plane-major: every bundle of plane 0, then of plane 1, ...  12-14 us FASTER than 4 on room0's batches (4096 x 64: 86 us)
-    //     and 10-35 us slower on freiburg1_desk's and scene0000's, with identical FETCH / atomic counters: not understood, not the default.
-    //   0 the 2-D (bundle, plane) grid of round 1 (= 3 without the slab reduction in the grid).
-    if (xcd_map == 1) {
-        const int xcd = bid & 7, j = bid >> 3;
-        const int q = (j / 3) * 8 + xcd;                     // (bundle, segment) pair handled by this XCD slot
-        if (q >= nbundles * 4) return;
-        const int seg = q & 3;                               // decoder * 2 + level
-        bidx = q >> 2;
-        pi = (seg >> 1) * 6 + (j % 3) * 2 + (seg & 1);
-    } else if (xcd_map == 3) {
-        bidx = bid % nbundles;
-        pi = bid / nbundles;
-        if (pi >= NPL) return;
-    } else if (xcd_map == 4) {
-        // auto: plane-major for a WIDE fan of rays from one origin, bundle-major otherwise.  Measured (profiles/r03/n_*): with the
-        // same pixels through lenses of different focal length, bundle-major costs 110 / 97 / 83 / 81 / 80 us at a horizontal field
-        // of view of 118 / 90 / 67 / 53 / 37 degrees where plane-major stays at 99 / 87 / 87 / 88 / 90 - the orders cross near 80
-        // degrees.  The fan's extent in each plane comes from the ray ordering kernel, through device memory (no host round trip);
-        // the SECOND largest of the three is the criterion (the largest is ~360 degrees in the plane the camera looks down on).
-        bool plane_major = false;
-        if (RENDER && perm) {
-            const float* fan = (const float*)(perm + (size_t)ESLAM_RAY_ORDERS * R);
-            const float f0 = fan[0], f1 = fan[1], f2 = fan[2];
-            const float second = fmaxf(fminf(f0, f1), fminf(fmaxf(f0, f1), f2));
-            plane_major = second >= 1.4f;
-        }
-        if (plane_major) { bidx = bid % nbundles; pi = bid / nbundles; }
-        else { pi = bid % NPL; bidx = bid / NPL; }
-        if (bidx >= nbundles || pi >= NPL) return;
-    } else {
-        bidx = bid;
-        pi = blockIdx.y;                                     // plane index in all_planes order
-        if (bidx >= nbundles) return;
+    //     order per orientation they no longer share rays, and the dealing is 0-10 us slower than bundle-major.
+    //   plane-major: every bundle of plane 0, then of plane 1, ...  12-14 us FASTER than bundle-major on room0's batches
+    //     (4096 x 64: 86 us) and 10-35 us slower on freiburg1_desk's and scene0000's, with identical FETCH / atomic counters.
+    // Measured (profiles/r03/n_*): with the same pixels through lenses of different focal length, bundle-major costs
+    // 110 / 97 / 83 / 81 / 80 us at a horizontal field of view of 118 / 90 / 67 / 53 / 37 degrees where plane-major stays at
+    // 99 / 87 / 87 / 88 / 90 - the orders cross near 80 degrees.  The fan's extent in each plane comes from the ray ordering
+    // kernel, through device memory (no host round trip); the SECOND largest of the three is the criterion (the largest is
+    // ~360 degrees in the plane the camera looks down on).
+    bool plane_major = false;
+    if (RENDER && perm) {
+        const float* fan = (const float*)(perm + (size_t)ESLAM_RAY_ORDERS * R);
+        const float f0 = fan[0], f1 = fan[1], f2 = fan[2];
+        const float second = fmaxf(fminf(f0, f1), fminf(fmaxf(f0, f1), f2));
+        plane_major = second >= 1.4f;
     }
+    int bidx, pi;
+    if (plane_major) { bidx = bid % nbundles; pi = bid / nbundles; }
+    else { pi = bid % NPL; bidx = bid / NPL; }
+    if (bidx >= nbundles || pi >= NPL) return;
     const int d = pi / 6, o = (pi % 6) >> 1, lvl = pi & 1;
     const eslam_plane_t& P = planes.p[pi];
     const int pw = P.w, ph = P.h;
@@ -476,12 +410,6 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
     const int nu = min(bundle, nunits - u0);
     const int n = nu * per;                                           // <= BM by construction of `bundle`
 
-#if SC_STAMPS
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = clock64();
-#define SSTAMP(i) { const unsigned long long now_ = clock64(); st_acc[i] += now_ - st_last; st_last = now_; }
-#else
-#define SSTAMP(i)
-#endif
     bool swap = false;
     if (threadIdx.x == 0) { sbox[0] = 0x7FFFFFFF; sbox[1] = -1; sbox[2] = 0x7FFFFFFF; sbox[3] = -1; }
     __syncthreads();
@@ -519,7 +447,6 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
             }
         }
     }
-    SSTAMP(0)
     bx0 = wave_min_i(bx0); bx1 = wave_max_i(bx1);
     by0 = wave_min_i(by0); by1 = wave_max_i(by1);
     if (lane == 0) {
@@ -540,8 +467,7 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
     // beyond float rounding.
     const int mmin = swap ? bymin : bxmin, mext = (swap ? bymax : bxmax) - mmin + 2;
     const int Mmin = swap ? bxmin : bymin, Mext = (swap ? bxmax : bymax) - Mmin + 1;
-    const bool counting = allow_counting && (int64_t)mext * Mext <= 4 * BM;
-    SSTAMP(1)
+    const bool counting = (int64_t)mext * Mext <= 4 * BM;
     if (counting) {
         constexpr int WPT = 2 * BM / NT;                       // counter words per thread in the scan
         for (int i = threadIdx.x; i < 2 * BM; i += NT) cnt[i] = 0u;
@@ -558,7 +484,6 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
             }
         }
         __syncthreads();
-        SSTAMP(2)
         // exclusive scan of the counters: thread t owns words [WPT t, WPT t + WPT)
         unsigned w[WPT], local = 0;
 #pragma unroll
@@ -581,7 +506,6 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
             run += lo16 + hi16;
         }
         __syncthreads();
-        SSTAMP(3)
         unsigned pos[SPT];
 #pragma unroll
         for (int k = 0; k < SPT; ++k) pos[k] = ((cnt[loc[k] >> 1] >> ((loc[k] & 1u) * 16u)) & 0xFFFFu) + tick[k];
@@ -684,8 +608,6 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
     }
     __syncthreads();
     }
-    SSTAMP(4)
-    if (dbg_mode == 2) return;
 
     // (3) walk: wave w owns sorted entries [256w, 256w+256), 64 at a time.  Per 64-entry block every lane fetches ONE
     // entry's (xy, g_feat row) and the block's cell boundaries become two 64-bit scalar masks (ballots): "entry starts a
@@ -725,17 +647,10 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
                         atomicAdd((float*)((char*)grad + o1), __builtin_nanf(""));
                     }
                 }
-            } else if (dbg_mode == 0 || dbg_mode == 5) {
-                if (!lower_half_only || hx == 0) {
-                    atomicAdd((float*)(gbytes + o0), (float)acc0);
-                    atomicAdd((float*)(gbytes + o1), (float)acc1);
-                }
-            } else if (dbg_mode == 6) {
-                if (!lower_half_only || hx == 0) {
-                    *(float*)(gbytes + o0) = (float)acc0;
-                    *(float*)(gbytes + o1) = (float)acc1;
-                }
-            } else if ((float)acc0 == 1.2345e30f) *(float*)(gbytes + o0) = (float)acc1;      // profiling only: walk without atomics
+            } else if (!lower_half_only || hx == 0) {
+                atomicAdd((float*)(gbytes + o0), (float)acc0);
+                atomicAdd((float*)(gbytes + o1), (float)acc1);
+            }
         }
     };
 
@@ -753,9 +668,7 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
         r.adjacent = __ballot(adj);
         return r;
     };
-#ifndef WALK_N
-#define WALK_N 8                   // entries per load-ahead group (2 groups in flight: 2*WALK_N VGPRs)
-#endif
+    constexpr int WALK_N = 8;      // entries per load-ahead group (2 groups in flight: 2*WALK_N VGPRs)
     const float2_t* const wlane = (const float2_t*)sw + hx;                    // + 2 * entry
     // A row load is TWO instructions: v_readlane of the row's byte offset into an SGPR, and a buffer load that adds that SGPR
     // (soffset) and the lane's channel offset (voffset) to the descriptor's base - the global_load form needed a VALU add
@@ -765,13 +678,12 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
 #define LOAD_HALF(buf, rec, half)                                                             \
     _Pragma("unroll") for (int t = 0; t < WALK_N; ++t) {                                      \
         const int rowb = __builtin_amdgcn_readlane((rec).row, (half) * WALK_N + t);           \
-        buf[t] = (dbg_mode >= 3 && dbg_mode <= 5) ? __int_as_float(rowb)                                       \
-                                 : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, cvoff, rowb, 0)); \
+        buf[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc, cvoff, rowb, 0)); \
     }
 #define WALK_HALF(buf, rec, half, ebase)                                                      \
     _Pragma("unroll") for (int t = 0; t < WALK_N; ++t) {                                      \
         const int idx = (half) * WALK_N + t;                                                  \
-        const float2_t w2 = (dbg_mode == 4) ? (float2_t){1.f, 2.f} : wlane[2 * ((ebase) + idx)]; \
+        const float2_t w2 = wlane[2 * ((ebase) + idx)];                                       \
         if (((idx < 32 ? fresh_lo : fresh_hi) >> (idx & 31)) & 1u) {     /* one s_bitcmp on a 32-bit scalar */ \
             if (((idx < 32 ? adj_lo : adj_hi) >> (idx & 31)) & 1u) {                          \
                 /* next cell along the minor axis: its first texel column is our second one - keep those sums */ \
@@ -831,12 +743,6 @@ __global__ __launch_bounds__(NT) void scatter_sort_kernel(const PlaneSet planes,
 #undef LOAD_HALF
 #undef WALK_HALF
     flush(false);
-    SSTAMP(5)
-#if SC_STAMPS
-    if (bid == 400 && threadIdx.x == 0)
-        printf("scatter stamps (cycles): cells %llu | box %llu | zero+tickets %llu | scan %llu | placement %llu | walk %llu\n", st_acc[0], st_acc[1],
-               st_acc[2], st_acc[3], st_acc[4], st_acc[5]);
-#endif
 }
 
 // deterministic mode: float gradient += shadow * 2^-44, shadow cleared (it is all zero again for the next call)
@@ -854,11 +760,6 @@ __global__ __launch_bounds__(256) void scatter_fixed_to_float_kernel(float* __re
 // ---------------------------------------------------------------------------------------------------------
 // host side (called from eslam_render_bwd.hip)
 // ---------------------------------------------------------------------------------------------------------
-static int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 int eslam_scatter_v2_init();
 
 // perm [R] <- rays ordered by direction; chunks of SORT_MAX rays are ordered independently
@@ -875,9 +776,8 @@ extern "C" int eslam_ray_order(const float* rays_o, const float* rays_d, int R, 
     // (16-bit keys were for the 2-D Hilbert order of round 2: 8 bits per axis.  The azimuth keys are one-dimensional: 14 bits = two
     // bins per ray at 8192 rays, and the histogram's zero fill and scan - 63 us of this kernel at 5000 rays with 16 bits - shrink 4x)
     const int key_bits = n <= 1024 ? 12 : 14;
-    static const int max_cams = env_int("ESLAM_RAY_ORDER_CAMERAS", 32);      // A/B switch: 0 = several origins always get the Morton order
     hipLaunchKernelGGL(ray_order_kernel, dim3(chunks, ESLAM_RAY_ORDERS), dim3(1024), ((size_t)1 << key_bits) / 2 * sizeof(unsigned), st,
-                       rays_o, rays_d, R, perm, key_bits, max_cams);
+                       rays_o, rays_d, R, perm, key_bits);
     return eslam_check_launch("ray_order_kernel");
 }
 
@@ -887,30 +787,23 @@ extern "C" int eslam_ray_order(const float* rays_o, const float* rays_d, int R, 
 // 1024-sample bundles walked by the same 512 threads (2 samples per thread, 128 sorted entries per wave): twice the
 // workgroups, half the walk.  Measured (profiles/r03/c_*): 200 x 32 (84 workgroups) 50.9 -> 30.6 us; 1024 x 64 (384) 47.2 ->
 // 50.6, 1024 x 96 (588) 55.1 -> 68.5, 2048 x 64 75.5 -> 89.7: from a few hundred workgroups on the kernel is throughput-bound
-// and the extra cell flushes of the smaller bundles cost more than the shorter walk gains.  ESLAM_SC_BUNDLE = 2048 / 1024 forces one of the two; 256 = the old 256-thread form of 1024
-// (profiling only).
-#ifndef SC_SMALL_WGS
+// and the extra cell flushes of the smaller bundles cost more than the shorter walk gains.
 #define SC_SMALL_WGS 192
-#endif
 static int scatter_bundle_size(int per, int nunits, int* bm_out) {
-    static const int forced = env_int("ESLAM_SC_BUNDLE", 0);
-    int bm = forced == 1024 || forced == 2048 || forced == 256 ? forced : 0;
-    if (eslam_deterministic()) bm = 2048;              // (the fixed-point kernel is instantiated for 2048 only)
-    if (bm == 0) {
+    int bm = 2048;                                     // (the fixed-point kernel is instantiated for 2048 only)
+    if (!eslam_deterministic()) {
         const int big = 2048 / per;
         const int nb = big > 0 ? (nunits + big - 1) / big : nunits;
         bm = (nb * NPL <= SC_SMALL_WGS && 1024 / per >= 1) ? 1024 : 2048;
     }
     *bm_out = bm;
-    return (bm == 2048 ? 2048 : 1024) / per;
+    return bm / per;
 }
 
-// whether the scatter launch of this mode can also run the decoder-gradient slab reduction (the production render path: one
-// kernel, XCD-mapped 1-D grid, 512 threads); the stand-alone dec_grad_reduce_kernel covers the rest
+// whether the scatter launch of this mode can also run the decoder-gradient slab reduction (the production render path);
+// the stand-alone dec_grad_reduce_kernel covers the rest
 bool eslam_scatter_can_reduce(bool render) {
-    static const int xcd_map = env_int("ESLAM_SC_XCDMAP", 4), dbg_mode = env_int("ESLAM_SC_MODE", 0), bm = env_int("ESLAM_SC_BUNDLE", 0);
-    static const int off = env_int("ESLAM_SC_NO_REDUCE", 0);
-    return render && !eslam_deterministic() && xcd_map && dbg_mode == 0 && bm != 256 && !off;
+    return render && !eslam_deterministic();
 }
 
 int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float* rays_o, const float* rays_d,
@@ -937,8 +830,6 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
             return 1;
         }
     }
-    static const int nosort = env_int("ESLAM_SC_NOSORT", 0), dbg_mode = env_int("ESLAM_SC_MODE", 0);       // A/B switch for profiling only
-    if (nosort) perm = nullptr;
     const int per = render ? S : 64;
     // 2048 samples per workgroup (512 threads) halve the number of cell flushes of 1024; S up to 256 -> >= 8 rays
     int bm;
@@ -948,12 +839,8 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
             eslam_set_error("scatter: plane %d has %d x %d cells, limit 2^21", i, planes[i].h, planes[i].w);
             return 1;
         }
-    static const int counting = env_int("ESLAM_SC_COUNTING", 1);   // A/B switch: 0 = always the bitonic network
-    static const int xcd_map = env_int("ESLAM_SC_XCDMAP", 4);      // A/B switch: 0 = plain (bundle, plane) grid
     const int nbundles = (nunits + bundle - 1) / bundle;
-    dim3 grid(nbundles, NPL);
-    if (xcd_map == 3 || xcd_map == 4) grid = dim3(nbundles * NPL, 1);
-    else if (xcd_map == 1) grid = dim3(((nbundles * 4 + 7) / 8) * 8 * 3, 1);
+    dim3 grid(nbundles * NPL);
     DecReduceArgs red_args = {};
     int red_blocks = 0;
     if (red) {
@@ -965,10 +852,9 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
         red_blocks = (2 * DEC_RED_COLBLOCKS + 7) / 8 * 8;
         grid.x += red_blocks;
     }
-#define LAUNCH_SC(RD, DB, NTv, PERM, SS, ...)                                                                              \
-    hipLaunchKernelGGL((scatter_sort_kernel<RD, DB, NTv, false, ##__VA_ARGS__>), grid, dim3(NTv), 0, st, ps, bnd, rays_o, rays_d, z_or_pts, \
-                       PERM, (int)R, SS, g_feat, bundle, counting, nbundles, xcd_map, (long long*)nullptr, ShadowOff{}, \
-                       red_args, red_blocks)
+#define LAUNCH_SC(RD, PERM, SS, ...)                                                                                      \
+    hipLaunchKernelGGL((scatter_sort_kernel<RD, false, ##__VA_ARGS__>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d, z_or_pts, \
+                       PERM, (int)R, SS, g_feat, bundle, nbundles, (long long*)nullptr, ShadowOff{}, red_args, red_blocks)
     if (eslam_deterministic()) {
         // fixed-point scatter into the int64 shadow, then shadow -> float gradients (DET in the kernel's header comment)
         ShadowOff so;
@@ -1017,13 +903,12 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
             shadow = shadows[devi];
         }
         if (render)
-            hipLaunchKernelGGL((scatter_sort_kernel<true, 0, 512, true>), grid, dim3(512), 0, st, ps, bnd, rays_o, rays_d,
-                               z_or_pts, perm, (int)R, S, g_feat, bundle, counting, nbundles, xcd_map, shadow, so,
-                               DecReduceArgs{}, 0);
+            hipLaunchKernelGGL((scatter_sort_kernel<true, true>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d,
+                               z_or_pts, perm, (int)R, S, g_feat, bundle, nbundles, shadow, so, DecReduceArgs{}, 0);
         else
-            hipLaunchKernelGGL((scatter_sort_kernel<false, 0, 512, true>), grid, dim3(512), 0, st, ps, bnd, rays_o, rays_d,
-                               z_or_pts, (const int*)nullptr, (int)R, 64, g_feat, bundle, counting, nbundles, xcd_map,
-                               shadow, so, DecReduceArgs{}, 0);
+            hipLaunchKernelGGL((scatter_sort_kernel<false, true>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d,
+                               z_or_pts, (const int*)nullptr, (int)R, 64, g_feat, bundle, nbundles, shadow, so,
+                               DecReduceArgs{}, 0);
         if (int rc = eslam_check_launch("scatter_sort_kernel<det>")) return rc;
         for (int i = 0; i < NPL; ++i) {
             const int64_t numel = (int64_t)ESLAM_C_DIM * planes[i].h * planes[i].w;
@@ -1033,18 +918,11 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
         return eslam_check_launch("scatter_fixed_to_float_kernel");
     }
     if (render) {
-        if (dbg_mode == 1) LAUNCH_SC(true, 1, 512, perm, S);
-        else if (dbg_mode == 2) LAUNCH_SC(true, 2, 512, perm, S);
-        else if (dbg_mode == 3) LAUNCH_SC(true, 3, 512, perm, S);
-        else if (dbg_mode == 4) LAUNCH_SC(true, 4, 512, perm, S);
-        else if (dbg_mode == 5) LAUNCH_SC(true, 5, 512, perm, S);
-        else if (dbg_mode == 6) LAUNCH_SC(true, 6, 512, perm, S);
-        else if (bm == 256) LAUNCH_SC(true, 0, 256, perm, S);
-        else if (bm == 1024) LAUNCH_SC(true, 0, 512, perm, S, 2);
-        else LAUNCH_SC(true, 0, 512, perm, S);
+        if (bm == 1024) LAUNCH_SC(true, perm, S, 2);
+        else LAUNCH_SC(true, perm, S);
     } else {
-        if (bm == 1024) LAUNCH_SC(false, 0, 512, (const int*)nullptr, 64, 2);
-        else LAUNCH_SC(false, 0, 512, (const int*)nullptr, 64);
+        if (bm == 1024) LAUNCH_SC(false, (const int*)nullptr, 64, 2);
+        else LAUNCH_SC(false, (const int*)nullptr, 64);
     }
 #undef LAUNCH_SC
     return eslam_check_launch("scatter_sort_kernel");

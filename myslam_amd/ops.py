@@ -254,10 +254,6 @@ _dec_param_cache = {}
 _side_streams = {}
 
 
-# ESLAM_PRECLEAR=0: the plane-gradient buffer is a torch.zeros in the backward pass instead of a memset on the side stream
-_PRECLEAR = os.environ.get("ESLAM_PRECLEAR", "1") == "1"
-
-
 def ray_order_async(rays_o, rays_d, grad_planes=None):
     """Launch eslam_ray_order on a side stream (it depends only on the rays, so it overlaps the samplers).
     Returns (perm int32 [3 R + 4]: one order per plane orientation + the fan's extent, stream to join before the order is used[, gradient views]).
@@ -274,7 +270,7 @@ def ray_order_async(rays_o, rays_d, grad_planes=None):
         side = _side_streams[dev.index] = torch.cuda.Stream(device=dev)
     perm = torch.empty(_hip.ray_order_words(R), dtype=torch.int32, device=dev)      # one order per plane orientation (+ the fan's extent)
     pre = None
-    if grad_planes is not None and _PRECLEAR and _grad_sink is None and not _keep_layout:      # (keep_layout: a sink will take the gradients)
+    if grad_planes is not None and _grad_sink is None and not _keep_layout:      # (keep_layout: a sink will take the gradients)
         pre = _alloc_plane_grads(grad_planes, zero=False)      # on the caller's stream: its allocator's memory
     _hip.stream_wait(dev, side, None)           # the rays - and any earlier use of that memory - come from work on the caller's stream
     with _hip.on_device(dev):
@@ -288,11 +284,6 @@ def ray_order_async(rays_o, rays_d, grad_planes=None):
         if t.data_ptr() != src.data_ptr():
             t.record_stream(side)        # a contiguous copy made on the current stream and read on the side stream
     return (perm, side) if pre is None else (perm, side, pre[1])
-
-
-# The forward kernel can process rays in the bundling order of the backward (ESLAM_FWD_ORDER=1).  Off: measured on
-# MI355X it is faster on the rays as given (119 vs 123-125 us at 4096x64 - sorted neighbours hit the same L2 channels).
-_FWD_USES_ORDER = os.environ.get("ESLAM_FWD_ORDER", "0") == "1"
 
 
 _fused_loss = None
@@ -325,7 +316,7 @@ def torch_ext():
 def ext_render_ok(rays_o, n_strat, rand):
     """Whether a render call may take the compiled path: the common case only (see eslam_torch_ext.cpp's header)."""
     return (rand is None and _USE_KERNEL_RNG and n_strat >= 3 and _half_planes is None and _grad_sink is None and not _keep_layout and
-            _rng_override is None and not _FWD_USES_ORDER and rays_o.is_cuda and torch_ext() is not None)
+            _rng_override is None and rays_o.is_cuda and torch_ext() is not None)
 
 
 def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_strat, n_imp, fl, relayout=False):
@@ -602,11 +593,9 @@ class RenderFn(torch.autograd.Function):
             order, side = order_in[0], order_in[1]
             if len(order_in) > 2 and needs:
                 ctx.pregrads = order_in[2]          # cleared on the side stream (ray_order_async), joined below
-            if _FWD_USES_ORDER:
-                _hip.stream_wait(dev, None, side)
-                side = None
-            # otherwise only the backward needs the order: the ordering kernel (side stream) is joined there, and the
-            # forward kernel starts as soon as the samplers are done
+            # only the backward needs the order: the forward kernel runs on the rays as given and starts as soon as the
+            # samplers are done (in the order of the backward it measured slower: 119 vs 123-125 us at 4096x64 - sorted
+            # neighbours hit the same L2 channels)
         fl = lossctx
         ctx.set_materialize_grads(False)
         ctx.lossctx = None
@@ -615,7 +604,7 @@ class RenderFn(torch.autograd.Function):
                 _hip.check(lib.eslam_render_fwd(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(rays_o),
                                                 _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(depth), _hip.ptr(rgb),
                                                 _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat),
-                                                _hip.ptr(order) if _FWD_USES_ORDER else None, _take_rng_bump(dev),
+                                                None, _take_rng_bump(dev),
                                                 _hip.stream_handle(dev)), "eslam_render_fwd")
             else:
                 _hip.require_gpu_f32("gt_depth", fl.gt_depth)
@@ -631,7 +620,7 @@ class RenderFn(torch.autograd.Function):
                 _hip.check(lib.eslam_render_fwd_loss(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(rays_o),
                                                      _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(depth),
                                                      _hip.ptr(rgb), _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat),
-                                                     _hip.ptr(order) if _FWD_USES_ORDER else None,
+                                                     None,
                                                      _hip.ptr(st.gt_depth), _hip.ptr(st.gt_color),
                                                      st.truncation, w5, _hip.ptr(mask),
                                                      _hip.ptr(_loss_scratch(dev, R)), _hip.ptr(fl.acc), _hip.ptr(fl.value),
@@ -641,7 +630,6 @@ class RenderFn(torch.autograd.Function):
             # join the side stream (ray order, gradient clear) BEHIND the forward kernel: the work beside it has overlapped,
             # and no fork is left dangling if this forward is never followed by a backward (or sits in a graph of its own)
             _hip.stream_wait(dev, None, side)
-            side = None
         if needs:
             ctx.bound6 = bound6
             ctx.order_stream = None

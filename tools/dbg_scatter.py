@@ -1,4 +1,4 @@
-"""Eager steps of one BASELINE.json workload for the rocprofv3 passes (kernel trace, PMC) and the ESLAM_SC_* scatter switches:
+"""Eager steps of one BASELINE.json workload for the rocprofv3 passes (kernel trace, PMC):
     python tools/dbg_scatter.py [scene rays n_strat n_imp zero_frac [lowp | camsN]]        (default: the bench workload, room0 4096 x 64;
     camsN: the batch of an N-camera keyframe window instead of one camera's rays)
 Also launches one calibration read of known size (a float32 sum over 256 MiB) so that collect_traffic.py can turn the L2
@@ -31,5 +31,4 @@ for _ in range(10):
     lib.eslam_profile_enable(1); step(); torch.cuda.synchronize(); lib.eslam_profile_read(buf); ts.append(buf[4])
 lib.eslam_profile_enable(0)
 for _ in range(3): float(cal.sum())
-env = {k: v for k, v in os.environ.items() if k.startswith('ESLAM_SC')}
-print(env, 'scatter ms median %.4f' % sorted(ts)[5], 'all kernels ms:', [round(x, 4) for x in buf])
+print('scatter ms median %.4f' % sorted(ts)[5], 'all kernels ms:', [round(x, 4) for x in buf])

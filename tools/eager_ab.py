@@ -1,5 +1,5 @@
 """Median eager (no hipGraph) step time of the bench workload: 7 repeats of 200 iterations after 30 warm-up steps.
-PIN=0,1 pins the process to those cores first; ESLAM_TORCH_STREAM_WAIT=1 uses torch's Stream.wait_stream for the side-stream fork / join."""
+PIN=0,1 pins the process to those cores first."""
 import sys, os, time
 if os.environ.get('PIN'):
     os.sched_setaffinity(0, {int(c) for c in os.environ['PIN'].split(',')})
@@ -15,4 +15,4 @@ for rep in range(7):
     t0 = time.perf_counter()
     for _ in range(200): wl.step()
     torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) / 200 * 1e3)
-print("pin", os.environ.get("PIN"), "affinity", len(os.sched_getaffinity(0)), os.environ.get("ESLAM_TORCH_STREAM_WAIT", "0"), "eager ms/step: median %.4f min %.4f" % (sorted(ts)[3], min(ts)))
+print("pin", os.environ.get("PIN"), "affinity", len(os.sched_getaffinity(0)), "eager ms/step: median %.4f min %.4f" % (sorted(ts)[3], min(ts)))
