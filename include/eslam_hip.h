@@ -235,6 +235,40 @@ int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* d
 int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                      const float* pts, int64_t N, int flags, float* raw, float* feat, eslam_stream_t stream);
 
+/* The SDF of an implicit grid: eslam_decode_fwd(ESLAM_DECODE_SDF_ONLY | flags) on the points (xs[ix], ys[iy], zs[iz]),
+ * which are never materialised.  Replaces the field half of src/utils/Mesher.py:196-217 (get_grid_uniform's points,
+ * Mesher.py:178-184, through eval_points in 500k batches, then z[~mask] = -1 with the frame hull's mask).
+ * xs [nx], ys [ny], zs [nz]: ascending float32 axes (np.linspace cast to float32, Mesher.py:170-180).
+ * vol [nx][ny][nz] (z fastest) = the reference's z.reshape(ny, nx, nz).transpose(1, 0, 2) (Mesher.py:224-226).
+ * halfspaces [n_halfspaces] float4 (nx, ny, nz, d), 16-byte aligned, may be NULL when n_halfspaces = 0: a point is inside
+ * the region when n.p + d <= 0 for all of them; vol is -1 outside the region.  flags: ESLAM_DECODE_MASK_OUTSIDE as for
+ * eslam_decode_fwd (-1 where the point is not strictly inside bound6); ESLAM_DECODE_SDF_ONLY is implied.
+ * Runs of 64 points along z are culled as segments: entirely outside the bound or one half-space -> -1 without a
+ * decode; both ends inside every half-space -> no per-point test.                                              */
+int eslam_sdf_grid(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                   const float* xs, const float* ys, const float* zs, int64_t nx, int64_t ny, int64_t nz,
+                   const float* halfspaces, int n_halfspaces, int flags, float* vol, eslam_stream_t stream);
+
+/* Marching cubes on vol [nx][ny][nz] (z fastest) at `level`.  Replaces skimage.measure.marching_cubes in
+ * src/utils/Mesher.py:222-239 (without Lewiner's interior-ambiguity resolution; tables: eslam_mc_tables.h).
+ * Two phases, one host sync in between:
+ *   eslam_mc_count  writes counts [2] (device int64) = (n_verts, n_faces); the caller reads them and allocates
+ *   eslam_mc_emit   fills verts [n_verts,3] float32 and faces [n_faces,3] int32; same vol, level and workspace.
+ * workspace: eslam_mc_workspace_bytes(nx, ny, nz) bytes (6 per grid point + 16 per 4096), kept between the calls.
+ * Output contract:
+ *   one vertex per crossing edge (one end < level, the other not) along +x, +y or +z from a grid point, shared by
+ *   every cube around it, ordered by that point's linear index, then axis x, y, z;  position
+ *   origin + (i + t) * spacing along the edge's axis, t = (level - v_lo) / (v_hi - v_lo), v_lo at the lower index
+ *   (origin, spacing float64 as Mesher.py:228-230,246);
+ *   faces ordered by cube (= its lower corner's linear index), then table order; (v1 - v0) x (v2 - v0) points toward
+ *   values >= level.  More than 2^31 - 1 vertices is an error of eslam_mc_emit.                                 */
+int64_t eslam_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int eslam_mc_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace, int64_t* counts,
+                   eslam_stream_t stream);
+int eslam_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, const double* origin3_host,
+                  const double* spacing3_host, const void* workspace, int64_t n_verts, int64_t n_faces, float* verts,
+                  int32_t* faces, eslam_stream_t stream);
+
 /* Backward of eslam_decode_fwd: g_raw [N,4] upstream, raw [N,4] the forward output.  Same gradient outputs as
  * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.                          */
 int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,

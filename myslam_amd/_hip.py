@@ -82,6 +82,10 @@ SIGNATURES = {
     "eslam_render_bwd_loss": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _BP, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_decode_fwd": (_i, [_PP, _DP, _BP, _vp, _i64, _i, _vp, _vp, _vp]),
+    "eslam_sdf_grid": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _vp, _vp]),
+    "eslam_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "eslam_mc_count": (_i, [_vp, _i64, _i64, _i64, _f, _vp, _vp, _vp]),
+    "eslam_mc_emit": (_i, [_vp, _i64, _i64, _i64, _f, ctypes.POINTER(_d), ctypes.POINTER(_d), _vp, _i64, _i64, _vp, _vp, _vp]),
     "eslam_decode_bwd": (_i, [_PP, _DP, _BP, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_mapping_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_loss_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),

@@ -229,9 +229,95 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
 // ---------------------------------------------------------------------------------------------------------
 // decode on free points: replaces reference src/networks/decoders.py:127-146 (and :87-105 when SDF_ONLY)
 // ---------------------------------------------------------------------------------------------------------
-template <bool CL, bool SDF_ONLY, bool SAVE>
+// Point sources of decode_fwd_kernel.  A source cuts its points into wave tiles of at most 64 consecutive output
+// indices, gives each point's world coordinates, and may classify a whole tile against a convex region.
+enum { TILE_IN = 0, TILE_TEST = 1, TILE_OUT = 2 };
+
+struct PointList {                      // pts [N,3] (Decoders.forward, Mesher.eval_points)
+    const float* pts;
+    int64_t N;
+    struct Tile { int64_t p0; int n; };
+    __device__ int64_t ntiles() const { return (N + 63) / 64; }
+    __device__ Tile tile(int64_t t) const { return Tile{t * 64, (int)min((int64_t)64, N - t * 64)}; }
+    __device__ void point(const Tile& t, int j, float& x, float& y, float& z) const {
+        const float* p = pts + (t.p0 + j) * 3;
+        x = p[0]; y = p[1]; z = p[2];
+    }
+    __device__ int classify(const Tile&, const Bound&, int) const { return TILE_IN; }
+    __device__ bool inside(const Tile&, float, float, float) const { return true; }
+};
+
+// The implicit grid (xs[ix], ys[iy], zs[iz]) of Mesher.get_grid_uniform, output [nx][ny][nz].  A tile is a run of at most
+// 64 points of one z-row, i.e. a segment (the axes ascend).  Half-spaces (n, d): a point is inside when n.p + d <= 0 for
+// all of them (an intersection, convex): a segment whose two ends are inside lies inside, one whose two ends are outside
+// the same half-space lies outside.
+struct GridPoints {
+    const float* xs; const float* ys; const float* zs;
+    int64_t nx, ny, nz, tpr;            // tpr: tiles per z-row
+    const float4_t* hs;
+    int nhs;
+    struct Tile { int64_t p0; int n; int64_t ix, iy, z0; };
+    __device__ int64_t ntiles() const { return nx * ny * tpr; }
+    __device__ Tile tile(int64_t t) const {
+        // the tile index is wave-uniform: say so, so that the tile's geometry and the half-space loads stay scalar
+        t = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
+                      (uint32_t)__builtin_amdgcn_readfirstlane((int)t));
+        const int64_t row = t / tpr, zt = t - row * tpr;
+        Tile r;
+        r.ix = row / ny;
+        r.iy = row - r.ix * ny;
+        r.z0 = zt * 64;
+        r.p0 = row * nz + r.z0;
+        r.n = (int)min((int64_t)64, nz - r.z0);
+        return r;
+    }
+    __device__ void point(const Tile& t, int j, float& x, float& y, float& z) const {
+        x = xs[t.ix]; y = ys[t.iy]; z = zs[t.z0 + j];
+    }
+    // the tile's class; each lane takes every 64th half-space, the wave votes
+    __device__ int classify(const Tile& t, const Bound& bnd, int mask_outside) const {
+        const float x = xs[t.ix], y = ys[t.iy], za = zs[t.z0], zb = zs[t.z0 + t.n - 1];
+        if (mask_outside && !(x < bnd.hi[0] && x > bnd.lo[0] && y < bnd.hi[1] && y > bnd.lo[1] && zb > bnd.lo[2] &&
+                              za < bnd.hi[2]))
+            return TILE_OUT;
+        bool both = false, one = false;
+        for (int k = threadIdx.x & 63; k < nhs; k += 64) {
+            bool oa, ob;
+            ends_outside(hs[k], x, y, za, zb, oa, ob);
+            both |= oa && ob;
+            one |= oa || ob;
+        }
+        if (__any(both)) return TILE_OUT;
+        return __any(one) ? TILE_TEST : TILE_IN;
+    }
+    __device__ static void ends_outside(const float4_t& h, float x, float y, float za, float zb, bool& oa, bool& ob) {
+        const float base = h[0] * x + h[1] * y + h[3];
+        oa = base + h[2] * za > 0.0f;
+        ob = base + h[2] * zb > 0.0f;
+    }
+    // per point of a TILE_TEST tile: only the half-spaces that split the tile's segment can reject a point of it
+    __device__ bool inside(const Tile& t, float x, float y, float z) const {
+        const float za = zs[t.z0], zb = zs[t.z0 + t.n - 1];
+        bool in = true;
+        for (int k0 = 0; k0 < nhs; k0 += 64) {
+            const int k = k0 + (threadIdx.x & 63);
+            bool oa = false, ob = false;
+            if (k < nhs) ends_outside(hs[k], x, y, za, zb, oa, ob);
+            uint64_t split = __ballot(oa != ob);
+            while (split) {
+                const int j = __builtin_ctzll(split);
+                split &= split - 1;
+                const float4_t h = hs[k0 + j];
+                if (h[0] * x + h[1] * y + h[3] + h[2] * z > 0.0f) in = false;
+            }
+        }
+        return in;
+    }
+};
+
+template <bool CL, bool SDF_ONLY, bool SAVE, typename Src>
 __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneSet planes, const eslam_decoders_t dec,
-                                                         const Bound bnd, const float* __restrict__ pts, int64_t N,
+                                                         const Bound bnd, const Src src,
                                                          float* __restrict__ raw, float* __restrict__ feat_out,
                                                          const int mask_outside) {
     __shared__ __attribute__((aligned(16))) float wlds[2 * DEC_LDS];
@@ -242,11 +328,17 @@ __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneS
     const int wave = threadIdx.x >> 6;
     const int r = lane & 15, q = lane >> 4;                                  // MFMA role
     const int gp = gather_point<CL>(lane), gq = gather_piece<CL>(lane);     // gather role
-    const int64_t ntiles = (N + 63) / 64;
+    const int64_t ntiles = src.ntiles();
 
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
-        const int64_t p0 = tile * 64;
-        const int nvalid = (int)min((int64_t)64, N - p0);
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
+        const typename Src::Tile tile = src.tile(t);
+        const int64_t p0 = tile.p0;
+        const int nvalid = tile.n;
+        const int cls = src.classify(tile, bnd, mask_outside);
+        if (cls == TILE_OUT) {          // (grid only) the whole tile is outside the bound or the half-spaces
+            if (lane < nvalid) raw[p0 + lane] = -1.0f;
+            continue;
+        }
         const int nblk = (nvalid + 15) >> 4;
         float4_t out[2];
 #pragma unroll
@@ -255,15 +347,17 @@ __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneS
 #pragma unroll 1
             for (int b = 0; b < nblk; ++b) {
                 const int oz0 = opaque_zero(b);
-                const int64_t pb = p0 + 16 * b + gp;
-                const int64_t pc = min(pb, N - 1);
-                const float px = norm_coord(pts[pc * 3 + 0], bnd.lo[0], bnd.hi[0]);
-                const float py = norm_coord(pts[pc * 3 + 1], bnd.lo[1], bnd.hi[1]);
-                const float pz = norm_coord(pts[pc * 3 + 2], bnd.lo[2], bnd.hi[2]);
+                const int j = 16 * b + gp;
+                const int64_t pb = p0 + j;
+                float wx, wy, wz;
+                src.point(tile, min(j, nvalid - 1), wx, wy, wz);
+                const float px = norm_coord(wx, bnd.lo[0], bnd.hi[0]);
+                const float py = norm_coord(wy, bnd.lo[1], bnd.hi[1]);
+                const float pz = norm_coord(wz, bnd.lo[2], bnd.hi[2]);
                 float feat[16];
                 gather_features<CL>(planes, d, px, py, pz, gq, feat, oz0);
                 if (SAVE) {
-                    if (pb < N) store_features(feat_out, pb, d, gq, feat);
+                    if (j < nvalid) store_features(feat_out, pb, d, gq, feat);
                 }
                 to_mfma_role<CL, 16>(feat, lane);
                 DecFrag f;
@@ -273,14 +367,22 @@ __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneS
                 mlp_out_accum(f, h2, b, r, out[d]);
             }
         }
+        bool keep = true;
+        if (cls == TILE_TEST) {         // (wave-uniform: every lane takes part in the half-space vote) Mesher.py:217
+            float x, y, z;
+            src.point(tile, min(lane, nvalid - 1), x, y, z);
+            keep = src.inside(tile, x, y, z);
+        }
         if (lane < nvalid) {
             float sdf = tanhf(out[0][0]);
             if (mask_outside) {     // Mesher.eval_points (Mesher.py:146-153): points not strictly inside the bound get -1
-                const float* pp = pts + (p0 + lane) * 3;
-                const bool in = pp[0] < bnd.hi[0] && pp[0] > bnd.lo[0] && pp[1] < bnd.hi[1] && pp[1] > bnd.lo[1] &&
-                                pp[2] < bnd.hi[2] && pp[2] > bnd.lo[2];
+                float x, y, z;
+                src.point(tile, lane, x, y, z);
+                const bool in = x < bnd.hi[0] && x > bnd.lo[0] && y < bnd.hi[1] && y > bnd.lo[1] && z < bnd.hi[2] &&
+                                z > bnd.lo[2];
                 if (!in) sdf = -1.0f;
             }
+            if (!keep) sdf = -1.0f;
             if (SDF_ONLY) {
                 raw[p0 + lane] = sdf;
             } else {
@@ -440,8 +542,9 @@ extern "C" int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoder
     const int64_t nwg = (ntiles + 3) / 4;
     dim3 grid((unsigned)(nwg < 8192 ? nwg : 8192)), block(256);
     hipStream_t st = (hipStream_t)stream;
+    const PointList src{pts, N};
 #define LAUNCH(CLv, SO, SV) \
-    hipLaunchKernelGGL((decode_fwd_kernel<CLv, SO, SV>), grid, block, 0, st, ps, *dec, bnd, pts, N, raw, feat, \
+    hipLaunchKernelGGL((decode_fwd_kernel<CLv, SO, SV, PointList>), grid, block, 0, st, ps, *dec, bnd, src, raw, feat, \
                        mask_outside)
     eslam_prof_begin(PROF_DECODE_FWD, st);
     if (sdf_only) {
@@ -457,4 +560,46 @@ extern "C" int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoder
 #undef LAUNCH
     eslam_prof_end(PROF_DECODE_FWD, st);
     return eslam_check_launch("decode_fwd_kernel");
+}
+
+extern "C" int eslam_sdf_grid(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                              const float* xs, const float* ys, const float* zs, int64_t nx, int64_t ny, int64_t nz,
+                              const float* halfspaces, int n_halfspaces, int flags, float* vol, eslam_stream_t stream) {
+    if (flags & ~(ESLAM_DECODE_SDF_ONLY | ESLAM_DECODE_MASK_OUTSIDE)) {
+        eslam_set_error("eslam_sdf_grid: unknown flags 0x%x", flags);
+        return 1;
+    }
+    if (nx < 0 || ny < 0 || nz < 0 || n_halfspaces < 0) {
+        eslam_set_error("eslam_sdf_grid: negative size");
+        return 1;
+    }
+    if (nx == 0 || ny == 0 || nz == 0) return 0;
+    if (!planes || !dec || !bound6_host || !xs || !ys || !zs || !vol || (n_halfspaces && !halfspaces)) {
+        eslam_set_error("eslam_sdf_grid: null argument");
+        return 1;
+    }
+    if ((uintptr_t)halfspaces % 16) {
+        eslam_set_error("eslam_sdf_grid: halfspaces must be 16-byte aligned (float4)");
+        return 1;
+    }
+    if (eslam_validate_planes(planes, 0, 6)) return 1;
+    PlaneSet ps;
+    for (int i = 0; i < NPL; ++i) ps.p[i] = planes[i >= 6 ? i - 6 : i];
+    const Bound bnd = make_bound(bound6_host);
+    const bool cl = eslam_planes_channels_last(planes, 0, 6);
+    GridPoints src;
+    src.xs = xs; src.ys = ys; src.zs = zs;
+    src.nx = nx; src.ny = ny; src.nz = nz; src.tpr = (nz + 63) / 64;
+    src.hs = (const float4_t*)halfspaces;
+    src.nhs = n_halfspaces;
+    const int64_t ntiles = nx * ny * src.tpr;
+    const int64_t nwg = (ntiles + 3) / 4;
+    dim3 grid((unsigned)(nwg < 8192 ? nwg : 8192)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int mask_outside = (flags & ESLAM_DECODE_MASK_OUTSIDE) ? 1 : 0;
+    if (cl) hipLaunchKernelGGL((decode_fwd_kernel<true, true, false, GridPoints>), grid, block, 0, st, ps, *dec, bnd, src, vol,
+                               nullptr, mask_outside);
+    else hipLaunchKernelGGL((decode_fwd_kernel<false, true, false, GridPoints>), grid, block, 0, st, ps, *dec, bnd, src, vol,
+                            nullptr, mask_outside);
+    return eslam_check_launch("decode_fwd_kernel<grid>");
 }

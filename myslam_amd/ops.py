@@ -1130,3 +1130,78 @@ class MappingLossFn(torch.autograd.Function):
                                                   _hip.ptr(g_rgb), _hip.ptr(g_sdf), _hip.ptr(g),
                                                   _hip.stream_handle(dev)), "eslam_loss_grad")
         return g_depth, g_rgb, g_sdf, None, None, None, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# meshing (reference src/utils/Mesher.py:188-262): the SDF on the marching-cubes grid, then marching cubes
+# ----------------------------------------------------------------------------------------------
+def sdf_grid(all_planes, decoders, axes, bound, halfspaces=None):
+    """vol [nx,ny,nz] float32 on the planes' device: the SDF at (xs[ix], ys[iy], zs[iz]), -1 where the point is not
+    strictly inside `bound` ([3,2]) and -1 outside the half-spaces [K,4] (n.p + d <= 0 inside).  axes: three ascending
+    float32 1-D tensors (np.linspace cast to float32, Mesher.py:170-180).  The reference's volume after its
+    reshape(ny, nx, nz).transpose(1, 0, 2) (Mesher.py:224-226)."""
+    dev = all_planes[0][0].device
+    xs, ys, zs = (_c(a.detach().to(dev, torch.float32).reshape(-1)) for a in axes)
+    for n, a in zip("xyz", (xs, ys, zs)):
+        _hip.require_gpu_f32(n + "s", a)
+    nx, ny, nz = xs.numel(), ys.numel(), zs.numel()
+    dec_bound6 = bound_to_host(decoders.bound)
+    bound6 = bound_to_host(bound)
+    same_bound = dec_bound6 == bound6
+    hs = None
+    if halfspaces is not None and halfspaces.shape[0] > 0:
+        hs = _c(halfspaces.detach().to(dev, torch.float32).reshape(-1, 4))
+    geo = tuple(all_planes[:3]) + tuple(all_planes[:3])
+    arr, _ = _hip.make_planes(tuple([t.detach() for t in grp] for grp in geo))
+    dec, keep = _hip.make_decoders([t.detach() for t in decoder_params(decoders)], beta_tensor(10, dev))
+    vol = torch.empty(nx, ny, nz, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_sdf_grid(arr, ctypes.byref(dec), _hip.make_bound(dec_bound6), _hip.ptr(xs), _hip.ptr(ys),
+                                             _hip.ptr(zs), nx, ny, nz, _hip.ptr(hs), 0 if hs is None else hs.shape[0],
+                                             2 if same_bound else 0, _hip.ptr(vol), _hip.stream_handle(dev)),
+                   "eslam_sdf_grid")
+    if not same_bound:       # a mesher bound that differs from the decoders' normalisation bound (as eval_points)
+        b = [(float(bound6[2 * k]), float(bound6[2 * k + 1])) for k in range(3)]
+        ins = [(a > lo) & (a < hi) for a, (lo, hi) in zip((xs, ys, zs), b)]
+        inside = ins[0][:, None, None] & ins[1][None, :, None] & ins[2][None, None, :]
+        vol.masked_fill_(~inside, -1.0)
+    return vol
+
+
+def mc_workspace_bytes(shape):
+    return int(_hip.lib().eslam_mc_workspace_bytes(*[int(n) for n in shape]))
+
+
+def mc_count(vol, level):
+    """Count phase of marching_cubes: (workspace, counts [2] int64 on the device) - nothing is synchronised."""
+    _hip.require_gpu_f32("vol", vol)
+    if vol.dim() != 3 or not vol.is_contiguous():
+        raise RuntimeError(f"marching_cubes: vol must be a contiguous [nx,ny,nz] tensor, got {tuple(vol.shape)}")
+    dev = vol.device
+    ws = torch.empty(mc_workspace_bytes(vol.shape), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_mc_count(_hip.ptr(vol), *vol.shape, float(level), _hip.ptr(ws), _hip.ptr(counts),
+                                             _hip.stream_handle(dev)), "eslam_mc_count")
+    return ws, counts
+
+
+def mc_emit(vol, level, origin, spacing, ws, n_verts, n_faces):
+    dev = vol.device
+    verts = torch.empty(n_verts, 3, device=dev)
+    faces = torch.empty(n_faces, 3, dtype=torch.int32, device=dev)
+    o3 = (ctypes.c_double * 3)(*[float(v) for v in origin])
+    s3 = (ctypes.c_double * 3)(*[float(v) for v in spacing])
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_mc_emit(_hip.ptr(vol), *vol.shape, float(level), o3, s3, _hip.ptr(ws), n_verts, n_faces,
+                                            _hip.ptr(verts), _hip.ptr(faces), _hip.stream_handle(dev)), "eslam_mc_emit")
+    return verts, faces
+
+
+def marching_cubes(vol, level, origin, spacing):
+    """(verts float32 [V,3], faces int32 [F,3]) on vol's device; vol a float32 [nx,ny,nz] GPU tensor.  One vertex per
+    crossing grid edge (welded), vertex = origin + (index + t) * spacing (float64 origin / spacing), faces wound so that
+    (v1 - v0) x (v2 - v0) points toward values >= level.  One host sync: reading (V, F) between the two phases."""
+    ws, counts = mc_count(vol, level)
+    n_verts, n_faces = (int(v) for v in counts.tolist())
+    return mc_emit(vol, level, origin, spacing, ws, n_verts, n_faces)

@@ -1,18 +1,28 @@
-"""The field query of the reference's Mesher on the HIP path.
+"""The reference's Mesher (src/utils/Mesher.py) on the HIP path: the field query, the frame hull and mesh extraction.
 
-Only `eval_points` (reference src/utils/Mesher.py:130-157) lives here - the caller that pushes the 500k-point batches
-of the marching-cubes grid through the decoders; grid construction, marching cubes and mesh clean-up stay with the
-reference (CPU, skimage / open3d / trimesh).  Bind it with
+Functions with the reference's signatures, to be bound onto its Mesher class one line each:
 
-    from myslam_amd.src.utils.Mesher import eval_points
-    Mesher.eval_points = eval_points
+    from myslam_amd.src.utils import Mesher as hip_mesher
+    Mesher.eval_points = hip_mesher.eval_points                        # Mesher.py:130-157
+    Mesher.get_bound_from_frames = hip_mesher.get_bound_from_frames    # Mesher.py:63-128
+    Mesher.get_mesh = hip_mesher.get_mesh                              # Mesher.py:188-262
 
-Same arguments, same [N,4] result (rgb, sdf with -1 outside the bound).  The bound test is folded into the decode
-kernel (ESLAM_DECODE_MASK_OUTSIDE), so a batch is one launch instead of a decode plus 8 mask / index ops, and all
+eval_points: same arguments, same [N,4] result (rgb, sdf with -1 outside the bound).  The bound test is folded into the
+decode kernel (ESLAM_DECODE_MASK_OUTSIDE), so a batch is one launch instead of a decode plus 8 mask / index ops, and all
 batches write into one output tensor (no torch.cat).
+
+get_bound_from_frames: the keyframes' valid depth back-projected (ops.image_rays) plus the camera centres, bounded by
+support half-spaces along a fixed set of 1024 directions and scaled by mesh_bound_scale - an outer approximation of the
+reference's convex hull of an open3d TSDF mesh.
+
+get_mesh: the grid of get_grid_uniform, the field on it with the bound and hull masks (ops.sdf_grid: the points are
+never materialised), marching cubes (ops.marching_cubes), vertex colours through eval_points, a binary PLY.  Needs none
+of skimage, open3d or trimesh.
 """
 import ctypes
+import math
 
+import numpy as np
 import torch
 
 from ... import _hip, ops
@@ -43,3 +53,167 @@ def eval_points(self, p, all_planes, decoders):
         inside = ((p < b[:, 1]) & (p > b[:, 0])).all(dim=1)
         out[~inside, -1] = -1
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# frame hull (Mesher.py:63-128)
+# ----------------------------------------------------------------------------------------------
+N_DIRECTIONS = 1024
+_dirs_cache = {}
+
+
+def support_directions():
+    """float64 [1024,3] unit vectors: the 26 directions of the 3x3x3 lattice (exact for box-shaped rooms) and a
+    Fibonacci sphere of 998 points.  A constant of the method, not an option."""
+    d = _dirs_cache.get("d")
+    if d is None:
+        lat = torch.tensor([(i, j, k) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1) if (i, j, k) != (0, 0, 0)],
+                           dtype=torch.float64)
+        n = N_DIRECTIONS - lat.shape[0]
+        k = torch.arange(n, dtype=torch.float64) + 0.5
+        z = 1.0 - 2.0 * k / n
+        r = torch.sqrt(1.0 - z * z)
+        phi = k * math.pi * (3.0 - math.sqrt(5.0))
+        fib = torch.stack([r * torch.cos(phi), r * torch.sin(phi), z], 1)
+        d = torch.cat([lat / lat.norm(dim=1, keepdim=True), fib], 0)
+        _dirs_cache["d"] = d
+    return d
+
+
+class FrameHull:
+    """The convex region {p : n.p + d <= 0 for every row (n, d) of halfspaces [K,4]} (float64)."""
+
+    def __init__(self, halfspaces):
+        self.halfspaces = halfspaces
+
+    def contains(self, points):
+        """bool [N] (trimesh.Trimesh.contains of the reference's hull, Mesher.py:211), on the points' device."""
+        p = torch.as_tensor(points)
+        hs = self.halfspaces.to(p.device, torch.float64)
+        out = torch.ones(p.shape[0], dtype=torch.bool, device=p.device)
+        for lo in range(0, p.shape[0], 1 << 16):
+            q = p[lo:lo + (1 << 16)].to(torch.float64)
+            out[lo:lo + q.shape[0]] = (q @ hs[:, :3].T + hs[:, 3]).le(0).all(dim=1)
+        return out
+
+
+def halfspaces_from_points(points, mesh_bound_scale=1.02, chunk=1 << 15):
+    """float64 [K,4] half-spaces (d, -h') bounding the point set [P,3] (any device): h(d) = max_p d.p over the fixed
+    directions, scaled about c, the mean of the distinct support points: h' = s h + (1 - s) d.c.  Contains every input
+    point (h' >= h >= d.c for s >= 1)."""
+    p = torch.as_tensor(points)
+    dev = p.device
+    dirs = support_directions().to(dev)
+    best = torch.full((dirs.shape[0],), -math.inf, dtype=torch.float64, device=dev)
+    arg = torch.zeros(dirs.shape[0], dtype=torch.int64, device=dev)
+    for lo in range(0, p.shape[0], chunk):
+        proj = p[lo:lo + chunk].to(torch.float64) @ dirs.T                 # [chunk, K]
+        v, i = proj.max(dim=0)
+        better = v > best
+        best = torch.where(better, v, best)
+        arg = torch.where(better, i + lo, arg)
+    support = torch.unique(arg)
+    c = p[support].to(torch.float64).mean(dim=0)
+    s = float(mesh_bound_scale)
+    h = s * best + (1.0 - s) * (dirs @ c)
+    return torch.cat([dirs, -h[:, None]], 1)
+
+
+def keyframe_points(self, keyframe_dict):
+    """float32 [P,3] on the keyframes' device: every valid depth pixel (> 0) back-projected with its est_c2w through
+    ops.image_rays (reference camera convention, src/common.py:183-201), then the camera centres."""
+    pts, cams = [], []
+    for kf in keyframe_dict:
+        c2w = kf["est_c2w"]
+        depth = kf["depth"]
+        ro, rd = ops.image_rays(int(self.H), int(self.W), float(self.fx), float(self.fy), float(self.cx), float(self.cy),
+                                c2w.to(depth.device, torch.float32))
+        d = depth.reshape(-1)
+        ok = d > 0
+        pts.append(ro[ok] + rd[ok] * d[ok, None])
+        cams.append(c2w[:3, 3].to(depth.device, torch.float32)[None])
+    return torch.cat(pts + cams, 0)
+
+
+def get_bound_from_frames(self, keyframe_dict, scale=1):
+    """Mesher.py:63-128 without open3d: a FrameHull around the keyframes' back-projected depth and camera centres.
+    (`scale` only set the reference's TSDF voxel size.)"""
+    return FrameHull(halfspaces_from_points(keyframe_points(self, keyframe_dict), self.mesh_bound_scale))
+
+
+# ----------------------------------------------------------------------------------------------
+# mesh (Mesher.py:158-262)
+# ----------------------------------------------------------------------------------------------
+def grid_axes(marching_cubes_bound, resolution):
+    """(x, y, z) float64 numpy axes of get_grid_uniform (Mesher.py:158-186): padding 0.05, nsteps rounded from the
+    float64 bound."""
+    b = torch.as_tensor(marching_cubes_bound, dtype=torch.float64)
+    padding = 0.05
+    out = []
+    for k in range(3):
+        n = ((b[k][1] - b[k][0] + 2 * padding) / resolution).round().int().item()
+        out.append(np.linspace(float(b[k][0]) - padding, float(b[k][1]) + padding, n))
+    return out
+
+
+NO_SURFACE = 'marching_cubes error. Possibly no surface extracted from the level set.'
+
+
+def extract_mesh(self, all_planes, decoders, keyframe_dict, device='cuda:0', color=True):
+    """get_mesh without the file: (vertices float32 [V,3] in scene units / self.scale, faces int32 [F,3],
+    colours float32 [V,3] or None) as numpy arrays, or None when the level set has no surface."""
+    with torch.no_grad():
+        dev = torch.device(device)
+        x, y, z = grid_axes(self.marching_cubes_bound, self.resolution)
+        axes = [torch.from_numpy(a).float().to(dev) for a in (x, y, z)]
+        hull = get_bound_from_frames(self, keyframe_dict, self.scale)
+        vol = ops.sdf_grid(all_planes, decoders, axes, self.bound, hull.halfspaces)
+        origin = (x[0], y[0], z[0])
+        spacing = (x[2] - x[1], y[2] - y[1], z[2] - z[1])
+        verts, faces = ops.marching_cubes(vol, self.level_set, origin, spacing)
+        del vol
+        if faces.shape[0] == 0:
+            return None
+        colours = None
+        if color:
+            colours = eval_points(self, verts, all_planes, decoders)[:, :3].cpu().numpy()
+        vertices = verts.cpu().numpy()
+        vertices /= self.scale
+        return vertices, faces.cpu().numpy(), colours
+
+
+def get_mesh(self, mesh_out_file, all_planes, decoders, keyframe_dict, device='cuda:0', color=True):
+    """Mesher.py:188-262: extract the mesh and write it as a binary PLY (write_ply).  No surface: the reference's message,
+    no file."""
+    m = extract_mesh(self, all_planes, decoders, keyframe_dict, device, color)
+    if m is None:
+        print(NO_SURFACE)
+        return
+    write_ply(mesh_out_file, *m)
+
+
+def write_ply(path, vertices, faces, colors=None):
+    """Binary little-endian PLY: vertex x y z float (+ red green blue alpha uchar, colour round(255 c) clipped, alpha
+    255), face `list uchar int vertex_indices`."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
+            "property float x", "property float y", "property float z"]
+    vfields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        head += ["property uchar red", "property uchar green", "property uchar blue", "property uchar alpha"]
+        vfields += [("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")]
+    head += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    vrec = np.empty(v.shape[0], dtype=vfields)
+    vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c = np.clip(np.round(255.0 * np.asarray(colors, dtype=np.float64)), 0, 255).astype(np.uint8).reshape(-1, 3)
+        vrec["red"], vrec["green"], vrec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+        vrec["alpha"] = 255
+    frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"] = 3
+    frec["v"] = f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vrec.tobytes())
+        fh.write(frec.tobytes())
