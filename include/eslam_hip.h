@@ -269,6 +269,57 @@ int eslam_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float le
                   const double* spacing3_host, const void* workspace, int64_t n_verts, int64_t n_faces, float* verts,
                   int32_t* faces, eslam_stream_t stream);
 
+/* Mesh culling: the visibility test of src/tools/cull_mesh.py:61-104 for a chunk of n_frames frames in one launch.
+ * For every vertex p of verts [n_verts,3] whose seen[p] is 0 and every frame k, with w2c[k] the 3x4 rows (float32,
+ * inverted from c2w on the host in float64) of w2c [n_frames][12] (device):
+ *   c = w2c[k] [p, 1];  a = fx (-c.x) + cx c.z;  b = fy c.y + cy c.z;  zz = c.z + 1e-5;  u = a / zz;  v = b / zz;
+ *   seen when -zz >= 0, 0 < u < W and 0 < v < H, and with depth_test (cfg['meshing']['eval_rec']) also
+ *   d + truncation >= -zz, d = the bilinear, zero-padded sample of depths[k] ([n_frames][depth_h][depth_w]) at pixel
+ *   (u (depth_w - 1) / W, v (depth_h - 1) / H) (grid_sample, align_corners=True, of the grid 2 (u / W, v / H) - 1).
+ * seen [n_verts] uint8 is ORed into (set to 1, never cleared).  depths may be NULL when depth_test is 0.            */
+int eslam_cull_vertices(const float* verts, int64_t n_verts, const float* depths, int n_frames, int depth_h, int depth_w,
+                        const float* w2c, float fx, float fy, float cx, float cy, int H, int W, float truncation,
+                        int depth_test, uint8_t* seen, eslam_stream_t stream);
+
+/* Exact nearest neighbours on a uniform grid of cubic cells: replaces scipy's cKDTree.query in
+ * src/tools/eval_recon.py:21-39 and open3d's correspondence search of registration_icp (eval_recon.py:42-56).
+ * Grid rule (eslam_nn_grid_plan, from the point count N and the bounding box [lo, hi] of the reference points):
+ *   E = the largest extent; E = 0 (one point, or all equal): one cell of edge 1.  Otherwise the m axes with extent
+ *   > 1e-6 E span the volume P (product of their extents), the target cell count is C = min(MAX_CELLS,
+ *   CELLS_PER_POINT * N), the edge h = (P / C)^(1/m), and dims[d] = max(1, ceil(extent[d] / h)) (flat axes: 1 cell).
+ *   While dims[0] dims[1] dims[2] > MAX_CELLS, h grows by 10 %.  The stored edge is the float32 just above h.
+ * Build: a counting sort of the reference points into cell order, kept in the workspace as float4 (x, y, z, index).
+ * Query: dist [n_query] = sqrt of the float32 squared distance to the nearest reference point, idx [n_query] its index;
+ *   equal distances go to the smaller index, so results are bit-identical run to run.  Exact for every query,
+ *   including ones far outside the box.  max_dist finite: only points with dist < max_dist count, none -> (inf, -1);
+ *   INFINITY = no limit.  flags: ESLAM_NN_INPUT_ORDER = process the queries in input order (no query workspace,
+ *   query_workspace may be NULL); by default they are first sorted by cell, the same counting sort.
+ * Workspaces: eslam_nn_workspace_bytes (kept between the build and every query), eslam_nn_query_workspace_bytes.      */
+#define ESLAM_NN_MAX_CELLS (1 << 24)
+#define ESLAM_NN_CELLS_PER_POINT 2
+#define ESLAM_NN_INPUT_ORDER 1
+typedef struct {
+    float lo[3];       /* the reference points' minimum corner */
+    float cell;        /* edge of the cubic cells             */
+    int32_t dims[3];   /* cells per axis                      */
+    int32_t reserved;
+} eslam_nn_grid_t;
+int eslam_nn_grid_plan(int64_t n_ref, const float* bbox6_host, eslam_nn_grid_t* grid);
+int64_t eslam_nn_workspace_bytes(const eslam_nn_grid_t* grid, int64_t n_ref);
+int eslam_nn_build(const float* ref, int64_t n_ref, const eslam_nn_grid_t* grid, void* workspace, eslam_stream_t stream);
+int64_t eslam_nn_query_workspace_bytes(const eslam_nn_grid_t* grid, int64_t n_query);
+int eslam_nn_query(const eslam_nn_grid_t* grid, const void* workspace, int64_t n_ref, const float* queries,
+                   int64_t n_query, float max_dist, int flags, void* query_workspace, float* dist, int32_t* idx,
+                   eslam_stream_t stream);
+
+/* The moments of one point-to-point ICP round (open3d's TransformationEstimationPointToPoint, eval_recon.py:52-54) over
+ * the correspondences i with idx[i] >= 0 and dist[i] < threshold, s = src[i], t = tgt[idx[i]]:
+ * out [17] (device, float64) = count, sum d^2, sum s (3), sum t (3), sum s t^T (9, row-major).  A fixed-order tree
+ * (no float atomics): bit-identical run to run.  workspace: eslam_icp_moments_workspace_bytes() bytes.           */
+int64_t eslam_icp_moments_workspace_bytes(void);
+int eslam_icp_moments(const float* src, const float* tgt, const float* dist, const int32_t* idx, int64_t n,
+                      float threshold, void* workspace, double* out, eslam_stream_t stream);
+
 /* Backward of eslam_decode_fwd: g_raw [N,4] upstream, raw [N,4] the forward output.  Same gradient outputs as
  * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.                          */
 int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,

@@ -37,12 +37,24 @@ class DecodersDesc(ctypes.Structure):
 
 
 PlaneArray = PlaneDesc * N_PLANES
+
+
+class NnGrid(ctypes.Structure):       # eslam_nn_grid_t
+    _fields_ = [("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("dims", ctypes.c_int32 * 3),
+                ("reserved", ctypes.c_int32)]
+
+
+NN_MAX_CELLS = 1 << 24       # ESLAM_NN_MAX_CELLS
+NN_CELLS_PER_POINT = 2       # ESLAM_NN_CELLS_PER_POINT
+NN_INPUT_ORDER = 1           # ESLAM_NN_INPUT_ORDER
+ICP_MOMENTS = 17             # eslam_icp_moments' out[]
 Bound6 = ctypes.c_float * 6
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _PP = ctypes.POINTER(PlaneDesc)
 _DP = ctypes.POINTER(DecodersDesc)
 _BP = ctypes.POINTER(ctypes.c_float)
+_GP = ctypes.POINTER(NnGrid)
 
 # name -> (restype, argtypes); must list every symbol declared in include/eslam_hip.h
 SIGNATURES = {
@@ -86,6 +98,14 @@ SIGNATURES = {
     "eslam_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "eslam_mc_count": (_i, [_vp, _i64, _i64, _i64, _f, _vp, _vp, _vp]),
     "eslam_mc_emit": (_i, [_vp, _i64, _i64, _i64, _f, ctypes.POINTER(_d), ctypes.POINTER(_d), _vp, _i64, _i64, _vp, _vp, _vp]),
+    "eslam_cull_vertices": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _i, _i, _f, _i, _vp, _vp]),
+    "eslam_nn_grid_plan": (_i, [_i64, _BP, _GP]),
+    "eslam_nn_workspace_bytes": (_i64, [_GP, _i64]),
+    "eslam_nn_build": (_i, [_vp, _i64, _GP, _vp, _vp]),
+    "eslam_nn_query_workspace_bytes": (_i64, [_GP, _i64]),
+    "eslam_nn_query": (_i, [_GP, _vp, _i64, _vp, _i64, _f, _i, _vp, _vp, _vp, _vp]),
+    "eslam_icp_moments_workspace_bytes": (_i64, []),
+    "eslam_icp_moments": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "eslam_decode_bwd": (_i, [_PP, _DP, _BP, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_mapping_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_loss_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),

@@ -244,6 +244,30 @@ __device__ __forceinline__ unsigned wave_incl_sum_u(unsigned x) {
     return (unsigned)v;
 }
 
+// exclusive scan of one value per thread over the workgroup (NT threads); `total` = the sum over all threads
+template <typename T, int NT>
+__device__ __forceinline__ T block_excl_scan(T v, T* lds, T& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    T x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) lds[w] = x;
+    __syncthreads();
+    T before = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < NT / 64; ++k) {
+        const T s = lds[k];
+        if (k < w) before += s;
+        tot += s;
+    }
+    __syncthreads();
+    total = tot;
+    return before + x - v;
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __device__ __forceinline__ float4_t mfma16(float a, float b, float4_t c) {

@@ -36,30 +36,6 @@ __device__ __forceinline__ void mc_coords(const McGrid& g, int64_t i, int64_t& i
     }
 }
 
-// exclusive scan of one value per thread over the workgroup (NT threads); `total` = the sum over all threads
-template <typename T, int NT>
-__device__ __forceinline__ T block_excl_scan(T v, T* lds, T& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    T before = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; ++k) {
-        const T s = lds[k];
-        if (k < w) before += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return before + x - v;
-}
-
 // vertex id of edge `e` (0..11) of the cube whose lower corner is point i
 __device__ __forceinline__ int mc_edge_vertex(const McGrid& g, int64_t i, int e, const int32_t* __restrict__ vbase,
                                               const uint8_t* __restrict__ ebits) {

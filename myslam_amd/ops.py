@@ -1205,3 +1205,139 @@ def marching_cubes(vol, level, origin, spacing):
     ws, counts = mc_count(vol, level)
     n_verts, n_faces = (int(v) for v in counts.tolist())
     return mc_emit(vol, level, origin, spacing, ws, n_verts, n_faces)
+
+
+# ----------------------------------------------------------------------------------------------
+# reconstruction evaluation (reference src/tools/cull_mesh.py, src/tools/eval_recon.py): culling, nearest neighbours,
+# ICP moments, surface sampling
+# ----------------------------------------------------------------------------------------------
+def _gpu_points(name, p, dev=None):
+    p = torch.as_tensor(p)
+    if dev is None:
+        dev = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    p = _c(p.detach().to(dev, torch.float32).reshape(-1, 3))
+    _hip.require_gpu_f32(name, p)
+    return p
+
+
+def cull_vertices(verts, frames, K, H, W, truncation, depth_test, chunk=32):
+    """bool [V] on verts' device: seen in at least one frame by the test of cull_mesh.py:61-104 (eslam_cull_vertices).
+    verts [V,3]; frames: an iterable of (depth [Hi,Wi], c2w [4,4]) (any device); K = (fx, fy, cx, cy); H, W the config's
+    image size; depth_test = cfg['meshing']['eval_rec'].  Frames are streamed `chunk` at a time: each c2w is inverted on
+    the host in float64 (one sync per chunk), the chunk's depths are stacked on the device, one launch per chunk."""
+    v = _gpu_points("verts", verts)
+    dev = v.device
+    fx, fy, cx, cy = (float(k) for k in K)
+    seen = torch.zeros(v.shape[0], dtype=torch.uint8, device=dev)
+    lib = _hip.lib()
+
+    def flush(depths, c2ws):
+        w2c = torch.linalg.inv(torch.stack([c.detach().to("cpu", torch.float64).reshape(4, 4) for c in c2ws]))
+        w2c = _c(w2c[:, :3, :].to(torch.float32).reshape(-1, 12).to(dev))
+        d = torch.stack([x.detach().to(dev, torch.float32) for x in depths]) if depth_test else None
+        hi, wi = (int(d.shape[1]), int(d.shape[2])) if d is not None else (0, 0)
+        with _hip.on_device(dev):
+            _hip.check(lib.eslam_cull_vertices(_hip.ptr(v), v.shape[0], _hip.ptr(d), len(c2ws), hi, wi, _hip.ptr(w2c),
+                                               fx, fy, cx, cy, int(H), int(W), float(truncation), 1 if depth_test else 0,
+                                               _hip.ptr(seen), _hip.stream_handle(dev)), "eslam_cull_vertices")
+
+    depths, c2ws = [], []
+    for depth, c2w in frames:
+        depths.append(depth)
+        c2ws.append(c2w)
+        if len(c2ws) == chunk:
+            flush(depths, c2ws)
+            depths, c2ws = [], []
+    if c2ws:
+        flush(depths, c2ws)
+    return seen.bool()
+
+
+class NNGrid:
+    """Exact nearest neighbours among the reference points `ref` [N,3] (float32 on the GPU): a uniform grid built once
+    (eslam_nn_grid_plan / eslam_nn_build; one host sync for the bounding box), queried any number of times.  Replaces
+    scipy's cKDTree(ref).query (eval_recon.py:21-39) and open3d's correspondence search."""
+
+    def __init__(self, ref):
+        self.ref = _gpu_points("ref", ref)
+        self.device = self.ref.device
+        n = self.ref.shape[0]
+        if n < 1:
+            raise RuntimeError("NNGrid: no reference points")
+        lo, hi = self.ref.aminmax(dim=0)
+        bbox = torch.stack([lo, hi], 1).reshape(-1).cpu()
+        self.grid = _hip.NnGrid()
+        lib = _hip.lib()
+        _hip.check(lib.eslam_nn_grid_plan(n, (ctypes.c_float * 6)(*bbox.tolist()), ctypes.byref(self.grid)),
+                   "eslam_nn_grid_plan")
+        self.ws = torch.empty(int(lib.eslam_nn_workspace_bytes(ctypes.byref(self.grid), n)), dtype=torch.uint8,
+                              device=self.device)
+        with _hip.on_device(self.device):
+            _hip.check(lib.eslam_nn_build(_hip.ptr(self.ref), n, ctypes.byref(self.grid), _hip.ptr(self.ws),
+                                          _hip.stream_handle(self.device)), "eslam_nn_build")
+
+    @property
+    def dims(self):
+        return tuple(self.grid.dims)
+
+    def query(self, q, max_dist=None, sort=True):
+        """(dist float32 [Q], idx int32 [Q]) on the grid's device: the distance to the nearest reference point and its
+        index (the smaller index among equal distances).  max_dist: only points with dist < max_dist count; a query with
+        none gets (inf, -1).  sort=False processes the queries in input order instead of cell order (same results)."""
+        q = _gpu_points("q", q, self.device)
+        nq = q.shape[0]
+        dist = torch.empty(nq, device=self.device)
+        idx = torch.empty(nq, dtype=torch.int32, device=self.device)
+        if nq == 0:
+            return dist, idx
+        lib = _hip.lib()
+        qws = None
+        if sort:
+            qws = torch.empty(int(lib.eslam_nn_query_workspace_bytes(ctypes.byref(self.grid), nq)), dtype=torch.uint8,
+                              device=self.device)
+        md = float("inf") if max_dist is None else float(max_dist)
+        with _hip.on_device(self.device):
+            _hip.check(lib.eslam_nn_query(ctypes.byref(self.grid), _hip.ptr(self.ws), self.ref.shape[0], _hip.ptr(q), nq, md,
+                                          0 if sort else _hip.NN_INPUT_ORDER, _hip.ptr(qws), _hip.ptr(dist), _hip.ptr(idx),
+                                          _hip.stream_handle(self.device)), "eslam_nn_query")
+        return dist, idx
+
+
+def icp_moments(src, tgt, dist, idx, threshold):
+    """float64 [17] on the device: count, sum d^2, sum s (3), sum t (3), sum s t^T (9) over the correspondences
+    (src[i], tgt[idx[i]]) with idx[i] >= 0 and dist[i] < threshold (eslam_icp_moments: a fixed-order reduction)."""
+    s = _gpu_points("src", src)
+    dev = s.device
+    t = _gpu_points("tgt", tgt, dev)
+    dist = _c(dist.to(dev, torch.float32))
+    idx = _c(idx.to(dev, torch.int32))
+    lib = _hip.lib()
+    ws = torch.empty(int(lib.eslam_icp_moments_workspace_bytes()), dtype=torch.uint8, device=dev)
+    out = torch.empty(_hip.ICP_MOMENTS, dtype=torch.float64, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(lib.eslam_icp_moments(_hip.ptr(s), _hip.ptr(t), _hip.ptr(dist), _hip.ptr(idx), s.shape[0], float(threshold),
+                                         _hip.ptr(ws), _hip.ptr(out), _hip.stream_handle(dev)), "eslam_icp_moments")
+    return out
+
+
+def sample_surface(verts, faces, n, seed=0):
+    """(samples float64 [n,3], face_index int64 [n]) on verts' device, as trimesh.sample.sample_surface: faces picked
+    with probability proportional to their area (float64 areas, cumulative sum, searchsorted of u * total, left side),
+    then two uniforms per sample, reflected to (1 - r1, 1 - r2) when r1 + r2 > 1, sample = v0 + r1 (v1 - v0) + r2 (v2 - v0).
+    Deviation: the draws come from a torch generator seeded with `seed`, not from numpy's global generator."""
+    v = torch.as_tensor(verts).detach().to(torch.float64).reshape(-1, 3)
+    f = torch.as_tensor(faces).detach().to(v.device, torch.int64).reshape(-1, 3)
+    if f.shape[0] == 0:
+        raise RuntimeError("sample_surface: the mesh has no faces")
+    dev = v.device
+    v0, v1, v2 = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    e1, e2 = v1 - v0, v2 - v0
+    area = 0.5 * torch.linalg.cross(e1, e2).norm(dim=1)
+    cum = torch.cumsum(area, 0)
+    g = torch.Generator(device=dev).manual_seed(int(seed))
+    pick = torch.rand(int(n), dtype=torch.float64, device=dev, generator=g) * area.sum()
+    fi = torch.searchsorted(cum, pick).clamp_(max=f.shape[0] - 1)
+    r = torch.rand(int(n), 2, dtype=torch.float64, device=dev, generator=g)
+    flip = r.sum(dim=1) > 1.0
+    r = torch.where(flip[:, None], 1.0 - r, r)
+    return v0[fi] + r[:, :1] * e1[fi] + r[:, 1:] * e2[fi], fi

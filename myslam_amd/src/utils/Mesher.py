@@ -217,3 +217,129 @@ def write_ply(path, vertices, faces, colors=None):
         fh.write(("\n".join(head) + "\n").encode("ascii"))
         fh.write(vrec.tobytes())
         fh.write(frec.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _ply_header(data):
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("not a PLY file")
+    end = data.index(b"\n", end) + 1
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", "replace").splitlines():
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info", "ply", "end_header"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if tok[1] == "list":             # (name, count type, item type)
+                elements[-1][2].append((tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+            else:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]], None))
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError(f"unsupported PLY format {fmt!r}")
+    return fmt, elements, end
+
+
+def _ply_read_binary(data, off, n, props, bo):
+    """One element of a binary PLY: ({scalar name: array [n]}, {list name: list of arrays}), offset after it."""
+    if all(lt is None for _, _, lt in props):
+        dt = np.dtype([(name, bo + t) for name, t, _ in props])
+        rec = np.frombuffer(data, dtype=dt, count=n, offset=off)
+        return {name: rec[name] for name, _, _ in props}, {}, off + n * dt.itemsize
+    # lists: try one uniform count per list (the common case: triangles), else walk the records
+    if n > 0:
+        fields, o, uniform = [], off, True
+        for name, t, lt in props:
+            if lt is None:
+                fields.append((name, bo + t))
+                o += np.dtype(t).itemsize
+            else:
+                k = int(np.frombuffer(data, dtype=bo + t, count=1, offset=o)[0])
+                fields += [(name + "#n", bo + t), (name, bo + lt, (k,))]
+                o += np.dtype(t).itemsize + k * np.dtype(lt).itemsize
+        dt = np.dtype(fields)
+        if off + n * dt.itemsize <= len(data):
+            rec = np.frombuffer(data, dtype=dt, count=n, offset=off)
+            uniform = all((rec[name + "#n"] == rec[name].shape[1]).all() for name, _, lt in props if lt is not None)
+            if uniform:
+                return ({name: rec[name] for name, _, lt in props if lt is None},
+                        {name: rec[name] for name, _, lt in props if lt is not None}, off + n * dt.itemsize)
+    scal = {name: np.empty(n, dtype=t) for name, t, lt in props if lt is None}
+    lists = {name: [] for name, _, lt in props if lt is not None}
+    for i in range(n):
+        for name, t, lt in props:
+            v = np.frombuffer(data, dtype=bo + t, count=1, offset=off)[0]
+            off += np.dtype(t).itemsize
+            if lt is None:
+                scal[name][i] = v
+            else:
+                lists[name].append(np.frombuffer(data, dtype=bo + lt, count=int(v), offset=off))
+                off += int(v) * np.dtype(lt).itemsize
+    return scal, lists, off
+
+
+def _ply_read_ascii(lines, pos, n, props):
+    scal = {name: np.empty(n, dtype=t) for name, t, lt in props if lt is None}
+    lists = {name: [] for name, _, lt in props if lt is not None}
+    for i in range(n):
+        tok = lines[pos + i].split()
+        j = 0
+        for name, t, lt in props:
+            if lt is None:
+                scal[name][i] = float(tok[j]) if t[0] == "f" else int(tok[j])
+                j += 1
+            else:
+                k = int(tok[j])
+                lists[name].append(np.array([float(x) if lt[0] == "f" else int(x) for x in tok[j + 1:j + 1 + k]]))
+                j += 1 + k
+    return scal, lists, pos + n
+
+
+def _fan(polys):
+    """Triangles [F,3] of polygons ([P,k] array or list of index arrays), each fanned from its first vertex."""
+    if isinstance(polys, np.ndarray):
+        k = polys.shape[1]
+        if k < 3:
+            return np.zeros((0, 3), dtype=np.int64)
+        return np.stack([np.stack([polys[:, 0], polys[:, j], polys[:, j + 1]], 1) for j in range(1, k - 1)], 1).reshape(-1, 3)
+    tris = [(p[0], p[j], p[j + 1]) for p in polys for j in range(1, len(p) - 1)]
+    return np.array(tris, dtype=np.int64).reshape(-1, 3)
+
+
+def read_ply(path):
+    """(vertices float32 [V,3], faces int64 [F,3], colours float32 [V,3] in [0, 1] or None) of a PLY file: ASCII or
+    binary (either byte order), any scalar vertex properties (x, y, z and red, green, blue are used; normals and other
+    properties are skipped), faces as a `vertex_indices` (or `vertex_index`) list of any count and index type, polygons
+    fan-triangulated from their first vertex, other elements skipped.  Reads what write_ply writes, bit for bit."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    fmt, elements, off = _ply_header(data)
+    lines, pos = None, 0
+    if fmt == "ascii":
+        lines = [ln for ln in data[off:].decode("ascii").splitlines() if ln.strip()]
+    bo = ">" if fmt == "binary_big_endian" else "<"
+    verts, faces, colors = None, np.zeros((0, 3), dtype=np.int64), None
+    for name, n, props in elements:
+        if fmt == "ascii":
+            scal, lists, pos = _ply_read_ascii(lines, pos, n, props)
+        else:
+            scal, lists, off = _ply_read_binary(data, off, n, props, bo)
+        if name == "vertex":
+            verts = np.stack([scal["x"], scal["y"], scal["z"]], 1).astype(np.float32)
+            if all(c in scal for c in ("red", "green", "blue")):
+                c = np.stack([scal["red"], scal["green"], scal["blue"]], 1)
+                colors = (c.astype(np.float32) / 255.0).astype(np.float32) if c.dtype.kind in "iu" else c.astype(np.float32)
+        elif name == "face":
+            key = "vertex_indices" if "vertex_indices" in lists else "vertex_index"
+            faces = _fan(lists[key]).astype(np.int64)
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    return verts, faces, colors
