@@ -427,10 +427,15 @@ int eslam_keep_best(const float* loss, const float* pose, int n, float* best, fl
  * order (per-workgroup slots instead of float atomics) and the plane-gradient scatter accumulates in 64-bit fixed point
  * (integer adds commute), so every output of the path is bitwise reproducible from run to run, at a lower speed.
  * Range of the fixed-point sums: units of 2^-44, so one contribution must stay below 2^18 = 2.6e5 in magnitude and a texel's
- * sum below 5.2e5; a contribution beyond the limit, or a NaN / Inf one, poisons the texel's float gradient with NaN instead
- * of being saturated silently.  One int64 shadow of the planes per device, allocated at the first (eager) use.
+ * sum below 5.2e5; a contribution beyond the limit, or a NaN / Inf one, poisons the float gradient of the texels it goes to
+ * (and of no other texel) with NaN instead of being saturated silently.  A sum that leaves the range while every contribution
+ * is inside it wraps undetected.  One int64 shadow of the planes per device, allocated at the first (eager) use.
  * eslam_loss_scratch_reset: back to the freshly-zeroed state, e.g. after a graph was aborted mid-flight.             */
 int eslam_deterministic(void);
+/* Samples per workgroup (1024 or 2048) the plane-gradient scatter uses for a batch of n rays with S samples each (render != 0)
+ * or of n free points (render == 0, S ignored): 2048, except in the default mode for batches that would make fewer than 192
+ * workgroups of 2048 samples.  Host arithmetic only, no launch; 0 for an empty or invalid batch. */
+int eslam_scatter_bundle_samples(int64_t n, int S, int render);
 
 /* Host-side helper of the Python layer (no reference counterpart): `waiter` waits for the work enqueued on `signaler` so
  * far - the fork / join of the side stream the ray ordering (eslam_ray_order, what the backward's scatter bundles by) runs

@@ -114,6 +114,7 @@ SIGNATURES = {
     "eslam_profile_name": (ctypes.c_char_p, [_i]),
     "eslam_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_deterministic": (_i, []),
+    "eslam_scatter_bundle_samples": (_i, [_i64, _i, _i]),
     "eslam_loss_scratch_floats": (_i64, [_i64]),
     "eslam_loss_scratch_reset": (_i, [_vp, _i64, _vp]),
     "eslam_loss_value": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp]),

@@ -321,6 +321,10 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
 #define FIX_SCALE 17592186044416.0f                  // 2^44: resolution 5.7e-14
 #define FIX_LIMIT 262144.0f                          // |one contribution| < 2^18: 2^62 in fixed point; a texel's SUM wraps beyond
                                                      // 2^63 / 2^44 = 5.2e5 - contributions past the limit poison the gradient (NaN)
+// What is and is not detected: a CONTRIBUTION that is NaN / Inf or at least FIX_LIMIT in magnitude sets det_bad in the lane that
+// holds it, and the flush of that lane's sums adds NaN to exactly the texels those sums go to (along a run of minor-axis
+// adjacent cells det_bad moves to the lower half-wave together with the carried column, so it never reaches a texel the
+// contribution did not touch).  A texel's SUM that leaves +-5.2e5 while every contribution is in range wraps undetected.
 struct ShadowOff { int64_t o[NPL]; };
 constexpr int SC_NT = 512;
 template <bool RENDER, bool DET, int SPT = 4>
@@ -687,10 +691,14 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
         if (((idx < 32 ? fresh_lo : fresh_hi) >> (idx & 31)) & 1u) {     /* one s_bitcmp on a 32-bit scalar */ \
             if (((idx < 32 ? adj_lo : adj_hi) >> (idx & 31)) & 1u) {                          \
                 /* next cell along the minor axis: its first texel column is our second one - keep those sums */ \
-                flush(true);          /* (det_bad stays: the carried column holds part of the cell's sums) */ \
+                flush(true);                                                                  \
                 const acc_t s0 = __shfl_xor(acc0, 32, WAVE), s1 = __shfl_xor(acc1, 32, WAVE); \
                 acc0 = hx ? (acc_t)0 : s0;                                                    \
                 acc1 = hx ? (acc_t)0 : s1;                                                    \
+                if (DET) {            /* det_bad travels with the carried column's sums and with nothing else */ \
+                    const int carried_bad = __shfl_xor((int)det_bad, 32, WAVE);               \
+                    det_bad = !hx && carried_bad;                                             \
+                }                                                                             \
             } else {                                                                          \
                 flush(false);                                                                 \
                 det_bad = false;                                                              \
@@ -798,6 +806,15 @@ static int scatter_bundle_size(int per, int nunits, int* bm_out) {
     }
     *bm_out = bm;
     return bm / per;
+}
+
+// Samples per workgroup (1024 or 2048) the scatter of such a batch is launched with: render mode n = rays of S samples each,
+// decode mode (S ignored) n = points.  Host arithmetic only; tests use it to see which instantiation a size exercises.
+extern "C" int eslam_scatter_bundle_samples(int64_t n, int S, int render) {
+    if (n <= 0 || (render && (S <= 0 || S > 256))) return 0;
+    int bm = 0;
+    (void)scatter_bundle_size(render ? S : 64, render ? (int)n : (int)((n + 63) / 64), &bm);
+    return bm;
 }
 
 // whether the scatter launch of this mode can also run the decoder-gradient slab reduction (the production render path);

@@ -5,6 +5,13 @@ scatter.  The mode is read once per process, so the checks run in child processe
     atomics of the scatter and of the loss sums leave run-to-run differences in the last bits - measured and printed);
   * with it, the ray-sharded mapper + fused Adam over 6 iterations agrees with the plain single-GPU loop at the 1e-5 that
     round 1 had to widen to 3e-4 (commit a6bd2ae): the widening covered atomic-order noise amplified by Adam, not an error.
+
+What this module does NOT cover: both sides of every comparison here run the deterministic kernels, so it shows that the mode is
+reproducible, not that it is right.  Measured with deliberately broken builds: the fixed-point scale off by a factor of two
+passes both tests here; a wrong shadow offset, a lost carried column or an unsummed loss slot are noticed only because the
+sharded mapper and the plain loop happen to reach the kernels with different batches, as a parameter difference with no
+hint of its cause.  The mode against the float64 oracle, and the bitwise properties only fixed point can have, are in
+tests/test_gpu_deterministic_parity.py.
 """
 import json
 import os
