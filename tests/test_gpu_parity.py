@@ -243,17 +243,7 @@ def test_whole_gradient_tensors_at_full_size(case):
     assert ok, (msg, int(amb.sum()))
     assert int(amb.sum()) <= 2e-3 * amb.numel()               # the exclusion stays an exception
 
-    def elementwise(name, a, b32, b64, floor):
-        """Comparator: the float32 oracle (the reference's arithmetic).  Where the float32 oracle itself is not pinned - it is
-        torch CPU code whose summation order changes with the thread count; on the 200x-weighted SDF terms it sits up to 1e-3
-        from the float64 oracle (conditioning note) - the float64 oracle bounds the comparison instead."""
-        a, b32, b64 = (np.asarray(t, dtype=np.float64) for t in (a, b32, b64))
-        cond = hp.rel_err(b32, b64)
-        assert hp.rel_err(a, b32) <= RTOL or hp.rel_err(a, b64) <= max(RTOL, 1.5 * cond), (name, hp.rel_err(a, b32), hp.rel_err(a, b64), cond)
-        ok, info = hp.elementwise_close(a, b32, rtol=RTOL, floor=floor)
-        if not ok:
-            bad = np.abs(a - b32) > RTOL * np.abs(b32) + floor * np.abs(b32).max()
-            assert (np.abs(a - b64)[bad] <= 1.5 * np.abs(b32 - b64)[bad] + RTOL * np.abs(b64)[bad] + floor * np.abs(b64).max()).all(), (name, info)
+    elementwise = lambda name, a, b32, b64, floor: hp.elementwise_vs_oracles(name, a, b32, b64, floor, RTOL)
     # floor: 3e-5 of the tensor's largest element - these are float32 sums of 2.6e5 - 7.9e5 float-atomic / MFMA-ordered
     # contributions; at 1e-5, 2 of the 1024 elements of c_linears.0.weight miss by 1.34x (4096 x 64, trained-like state)
     for k, p in r["dec"].named_parameters():
