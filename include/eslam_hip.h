@@ -320,6 +320,60 @@ int64_t eslam_icp_moments_workspace_bytes(void);
 int eslam_icp_moments(const float* src, const float* tgt, const float* dist, const int32_t* idx, int64_t n,
                       float threshold, void* workspace, double* out, eslam_stream_t stream);
 
+/* Depth images of a triangle mesh for a chunk of n_views views in one call: replaces open3d's visualiser in
+ * src/tools/eval_recon.py:177-201 (capture_depth_float_buffer(True) with mesh_show_back_face and set_constant_z_far(20)).
+ * verts [n_verts,3] float32, faces [n_faces,3] int32, w2c [n_views][12] the 3x4 rows (float32, inverted from c2w on the
+ * host in float64) of the reference's param.extrinsic = inv(c2w): the camera looks along +z, x right, y down.
+ * depth [n_views][H][W] float32 = the camera-space z of the nearest surface at each pixel centre, 0 where nothing is hit.
+ * Per view, with v0, v1, v2 a triangle's vertices in the camera frame (v = w2c [p, 1], float32) and
+ * d = ((i - cx) / fx, (j - cy) / fy, 1) the ray of pixel (column i, row j):
+ *   edge functions  E0 = d . (v1 x v2),  E1 = d . (v2 x v0),  E2 = d . (v0 x v1), each cross product evaluated from
+ *                   the edge's smaller end (camera-space x, then y, then z) as lo x (hi - lo), negated when that end is
+ *                   v_j: the same value without the cancellation of two long vectors, and the same bits up to the sign
+ *                   in the two triangles that share the edge;
+ *   covered         when E0, E1, E2 >= 0 or E0, E1, E2 <= 0: no back-face culling, and zero counts as inside, so a
+ *                   shared edge leaves no hole;
+ *   depth           z = (n . v0) / (n . d),  n = (v1 - v0) x (v2 - v0);  n . d = 0 (ray in the plane) is no hit;
+ *   a hit counts    when z_near <= z <= z_far; the pixel keeps the smallest such z over all triangles.
+ * There is no perspective divide of vertices and so no near-plane clipping: a triangle that straddles the camera plane
+ * renders its part beyond z_near.  Skipped: a triangle with n = 0, one whose largest vertex z is below z_near or whose
+ * smallest is above z_far, one with a vertex index outside [0, n_verts).  Pixel box: the projections' bounds widened by
+ * 0.01 px, clamped to the image; with a vertex at z <= z_near, the bounds of the triangle's part beyond z_near / 2 (the
+ * polygon cut by that plane, its corners projected) widened by 1 px.
+ * The z-buffer is the output itself, as uint32 holding the float's bits (positive floats order as their bit patterns):
+ * cleared to 0x7f800000, resolved with atomicMin, untouched pixels turned into 0 by a last pass - all inside the call.
+ * min is order-independent: two calls give bit-identical images, and a chunk equals its views rendered one by one.
+ * large_area: a triangle whose pixel box holds more than large_area pixels is cut into 64 x 64 pixel tiles, queued and
+ * rasterised a wave per tile; a smaller one is rasterised by the lane that set it up.  <= 0 = ESLAM_RASTER_LARGE_AREA.
+ * The images do not depend on it.  workspace: eslam_raster_workspace_bytes(n_faces, n_views, H, W) bytes, any contents
+ * (a counter and a queue of at most 2^19 tiles per view; tiles beyond the queue are rasterised by their triangle's lane).
+ * H, W <= 16384.  Deviation: z_near is the caller's constant (ESLAM_RASTER_Z_NEAR in our metric); open3d derives its
+ * near plane from the scene's bounding box.                                                                        */
+#define ESLAM_RASTER_LARGE_AREA 64
+#define ESLAM_RASTER_Z_NEAR 0.01f
+#define ESLAM_RASTER_Z_FAR 20.0f
+int64_t eslam_raster_workspace_bytes(int64_t n_faces, int n_views, int H, int W);
+int eslam_raster_depth(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* w2c,
+                       int n_views, float fx, float fy, float cx, float cy, int H, int W, float z_near, float z_far,
+                       int large_area, void* workspace, float* depth, eslam_stream_t stream);
+
+/* out [n_views] (device, float64) = per view the sum over its n_pixels pixels of |a - b|, a and b [n_views][n_pixels]
+ * float32 (np.abs(gt_depth - ours_depth) of eval_recon.py:203 before the mean; empty pixels are 0 in both images and
+ * take part).  A fixed-order tree in float64 (no float atomics): bit-identical run to run.
+ * workspace: eslam_depth_l1_workspace_bytes(n_views) bytes.  n_views <= 65535.                                       */
+int64_t eslam_depth_l1_workspace_bytes(int n_views);
+int eslam_depth_l1(const float* a, const float* b, int n_views, int64_t n_pixels, void* workspace, double* out,
+                   eslam_stream_t stream);
+
+/* check_proj (src/tools/eval_recon.py:59-85) for a chunk of n_views candidate views: seen[k] (uint8, ORed into: set
+ * to 1, never cleared) when any point of points [n_points,3] projects into view k.  w2c [n_views][12]: the 3x4 rows
+ * (float32) of the float64 inverse, taken on the host, of c2w[k] with its columns 1 and 2 negated (eval_recon.py:64-68).
+ * For point p and view k, in float32:
+ *   c = w2c[k] [p, 1];  c.x *= -1;  a = fx c.x + cx c.z;  b = fy c.y + cy c.z;  z = c.z + 1e-5;  u = a / z;  v = b / z;
+ *   p is in view when 0 <= -z, 0 < u < W and 0 < v < H                                         (edge = 0).          */
+int eslam_views_see_points(const float* points, int64_t n_points, const float* w2c, int n_views, float fx, float fy,
+                           float cx, float cy, int H, int W, uint8_t* seen, eslam_stream_t stream);
+
 /* Backward of eslam_decode_fwd: g_raw [N,4] upstream, raw [N,4] the forward output.  Same gradient outputs as
  * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.                          */
 int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,

@@ -48,6 +48,9 @@ NN_MAX_CELLS = 1 << 24       # ESLAM_NN_MAX_CELLS
 NN_CELLS_PER_POINT = 2       # ESLAM_NN_CELLS_PER_POINT
 NN_INPUT_ORDER = 1           # ESLAM_NN_INPUT_ORDER
 ICP_MOMENTS = 17             # eslam_icp_moments' out[]
+RASTER_LARGE_AREA = 64       # ESLAM_RASTER_LARGE_AREA
+RASTER_Z_NEAR = 0.01         # ESLAM_RASTER_Z_NEAR
+RASTER_Z_FAR = 20.0          # ESLAM_RASTER_Z_FAR
 Bound6 = ctypes.c_float * 6
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
@@ -106,6 +109,11 @@ SIGNATURES = {
     "eslam_nn_query": (_i, [_GP, _vp, _i64, _vp, _i64, _f, _i, _vp, _vp, _vp, _vp]),
     "eslam_icp_moments_workspace_bytes": (_i64, []),
     "eslam_icp_moments": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
+    "eslam_raster_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "eslam_raster_depth": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
+    "eslam_depth_l1_workspace_bytes": (_i64, [_i]),
+    "eslam_depth_l1": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "eslam_views_see_points": (_i, [_vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
     "eslam_decode_bwd": (_i, [_PP, _DP, _BP, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_mapping_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_loss_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),

@@ -1341,3 +1341,93 @@ def sample_surface(verts, faces, n, seed=0):
     flip = r.sum(dim=1) > 1.0
     r = torch.where(flip[:, None], 1.0 - r, r)
     return v0[fi] + r[:, :1] * e1[fi] + r[:, 1:] * e2[fi], fi
+
+
+# ----------------------------------------------------------------------------------------------
+# the 2D reconstruction metric (reference src/tools/eval_recon.py:59-85, 127-207): depth rasteriser, depth L1, check_proj
+# ----------------------------------------------------------------------------------------------
+def _w2c_rows(c2ws, dev, flip_yz=False):
+    """float32 [n,12] on dev: the 3x4 rows of inverse(c2w) taken on the host in float64 (one sync); flip_yz negates
+    columns 1 and 2 of each c2w first (check_proj, eval_recon.py:64-68)."""
+    c = torch.as_tensor(c2ws).detach().to("cpu", torch.float64).reshape(-1, 4, 4).clone()
+    if flip_yz:
+        c[:, :3, 1] *= -1.0
+        c[:, :3, 2] *= -1.0
+    return _c(torch.linalg.inv(c)[:, :3, :].to(torch.float32).reshape(-1, 12).to(dev))
+
+
+def render_mesh_depth(verts, faces, c2ws, K, H, W, z_near=_hip.RASTER_Z_NEAR, z_far=_hip.RASTER_Z_FAR, chunk=32,
+                      large_area=0):
+    """float32 [n,H,W] on the GPU: the depth images of the mesh (verts [V,3] float32, faces [F,3]) from the cameras
+    c2ws [n,4,4] (camera looks along +z, x right, y down: the reference's param.extrinsic = inv(c2w)), K = (fx, fy, cx, cy):
+    camera-space z of the nearest surface at each pixel centre within [z_near, z_far], 0 where nothing is hit
+    (eslam_raster_depth; what open3d's capture_depth_float_buffer(True) returns in eval_recon.py:191,199).  Views are
+    rendered `chunk` at a time, one call each; the poses are inverted on the host in float64.  large_area: the size
+    threshold between the two triangle paths in pixels (0 = the library's default; the images do not depend on it)."""
+    v = torch.as_tensor(verts)
+    _hip.require_gpu_f32("verts", v)
+    dev = v.device
+    v = _c(v.detach().reshape(-1, 3))
+    f = torch.as_tensor(faces)
+    if not f.is_cuda:
+        raise RuntimeError(f"faces: expected a tensor on the GPU (got device {f.device}); the rasteriser has no CPU fallback")
+    f = _c(f.detach().to(dev, torch.int32).reshape(-1, 3))
+    fx, fy, cx, cy = (float(k) for k in K)
+    H, W, chunk = int(H), int(W), max(1, int(chunk))
+    w2c = _w2c_rows(c2ws, dev)
+    n = w2c.shape[0]
+    out = torch.empty(n, H, W, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    lib = _hip.lib()
+    nb = int(lib.eslam_raster_workspace_bytes(f.shape[0], min(chunk, n), H, W))
+    if nb < 0:
+        raise RuntimeError(f"render_mesh_depth: bad sizes ({f.shape[0]} faces, image {W} x {H})")
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    with _hip.on_device(dev):
+        for lo in range(0, n, chunk):
+            k = min(chunk, n - lo)
+            _hip.check(lib.eslam_raster_depth(_hip.ptr(v), v.shape[0], _hip.ptr(f), f.shape[0], _hip.ptr(w2c[lo:]), k, fx, fy,
+                                              cx, cy, H, W, float(z_near), float(z_far), int(large_area), _hip.ptr(ws),
+                                              _hip.ptr(out[lo:]), _hip.stream_handle(dev)), "eslam_raster_depth")
+    return out
+
+
+def depth_l1(a, b):
+    """float64 [n] on the device: per view the sum over the pixels of |a - b|, a and b float32 [n,H,W] (eslam_depth_l1:
+    a fixed-order float64 reduction)."""
+    _hip.require_gpu_f32("a", a)
+    _hip.require_gpu_f32("b", b)
+    if a.shape != b.shape or a.dim() != 3 or a.device != b.device:
+        raise RuntimeError(f"depth_l1: expected two [n,H,W] stacks of one shape on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = _c(a.detach()), _c(b.detach())
+    dev = a.device
+    n, npix = a.shape[0], a.shape[1] * a.shape[2]
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    lib = _hip.lib()
+    with _hip.on_device(dev):
+        for lo in range(0, n, 65535):
+            k = min(65535, n - lo)
+            ws = torch.empty(int(lib.eslam_depth_l1_workspace_bytes(k)), dtype=torch.uint8, device=dev)
+            _hip.check(lib.eslam_depth_l1(_hip.ptr(a[lo:]), _hip.ptr(b[lo:]), k, npix, _hip.ptr(ws), _hip.ptr(out[lo:]),
+                                          _hip.stream_handle(dev)), "eslam_depth_l1")
+    return out
+
+
+def views_see_points(points, c2ws, K, H, W):
+    """bool [n] on the points' device: view k sees at least one of points [N,3] (float32 on the GPU) by the test of the
+    reference's check_proj (eval_recon.py:59-85; eslam_views_see_points), c2ws [n,4,4] in the reference's convention there."""
+    p = torch.as_tensor(points)
+    _hip.require_gpu_f32("points", p)
+    p = _c(p.detach().reshape(-1, 3))
+    dev = p.device
+    fx, fy, cx, cy = (float(k) for k in K)
+    w2c = _w2c_rows(c2ws, dev, flip_yz=True)
+    n = w2c.shape[0]
+    seen = torch.zeros(n, dtype=torch.uint8, device=dev)
+    if n and p.shape[0]:
+        with _hip.on_device(dev):
+            _hip.check(_hip.lib().eslam_views_see_points(_hip.ptr(p), p.shape[0], _hip.ptr(w2c), n, fx, fy, cx, cy, int(H),
+                                                         int(W), _hip.ptr(seen), _hip.stream_handle(dev)),
+                       "eslam_views_see_points")
+    return seen.bool()

@@ -1,15 +1,19 @@
-"""The reference's 3D reconstruction metrics (src/tools/eval_recon.py) without trimesh, open3d or scipy: exact nearest
-neighbours on a GPU grid (ops.NNGrid, in place of cKDTree), open3d's point-to-point ICP loop with its correspondence
-moments reduced on the GPU (ops.icp_moments) and the 3x3 solve on the host, trimesh's surface sampling
-(ops.sample_surface), meshes read as PLY (Mesher.read_ply).
+"""The reference's reconstruction metrics (src/tools/eval_recon.py) without trimesh, open3d, scipy or a GL context:
+exact nearest neighbours on a GPU grid (ops.NNGrid, in place of cKDTree), open3d's point-to-point ICP loop with its
+correspondence moments reduced on the GPU (ops.icp_moments) and the 3x3 solve on the host, trimesh's surface sampling
+(ops.sample_surface), meshes read as PLY (Mesher.read_ply), and for the 2D metric a depth rasteriser
+(ops.render_mesh_depth, in place of open3d's visualiser), the per-view |difference| sums (ops.depth_l1) and the
+unseen-points test of a batch of candidate views (ops.views_see_points).
 
-    python -m myslam_amd.src.tools.eval_recon --rec_mesh REC.ply --gt_mesh GT.ply -3d
+    python -m myslam_amd.src.tools.eval_recon --rec_mesh REC.ply --gt_mesh GT.ply -2d -3d
 
 accuracy / completion / completion_ratio take numpy arrays or torch tensors [N,3] and return a float, as the reference's
-(eval_recon.py:21-39).  Deviations: the samples are drawn from a torch generator seeded with `seed` (the reconstructed
+(eval_recon.py:21-39).  Deviations, 3D: the samples are drawn from a torch generator seeded with `seed` (the reconstructed
 mesh's with seed, the ground truth's with seed + 1) instead of numpy's global generator; distances are float32 (the
-square root of the float32 squared distance) where cKDTree's are float64.  The 2D depth-L1 metric (eval_recon.py:127+)
-is not implemented: it needs a triangle rasteriser.
+square root of the float32 squared distance) where cKDTree's are float64.  Deviations, 2D: the
+views come from a seeded numpy Generator instead of `random` and numpy's global state; the camera box is the smallest
+of a fixed candidate set of orientations (get_cam_position) where trimesh searches the convex hull; the near plane is
+the constant Z_NEAR where open3d derives one from the scene's bounding box.
 """
 import argparse
 
@@ -151,9 +155,204 @@ def calc_3d_metric(rec_meshfile, gt_meshfile, align=True, num_points=450000):
     return r
 
 
+# ----------------------------------------------------------------------------------------------
+# the 2D metric: depth L1 over random views inside the room (eval_recon.py:59-85, 116-207)
+# ----------------------------------------------------------------------------------------------
+IMG_H = IMG_W = 500          # eval_recon.py:132-138
+FOCAL = 300.0
+IMG_CX = IMG_H / 2.0 - 0.5
+IMG_CY = IMG_W / 2.0 - 0.5
+Z_NEAR = ops._hip.RASTER_Z_NEAR      # ours (open3d derives its near plane from the bounding box)
+Z_FAR = ops._hip.RASTER_Z_FAR        # ctr.set_constant_z_far(20)
+BOX_ANGLES = 90              # get_cam_position: candidate rotations of 1 degree about each axis of each base frame
+VIEW_BATCH = 64              # sample_views: candidates drawn and tested per call
+
+
+def viewmatrix(z, up, pos):
+    """eval_recon.py:13-19: the 3x4 camera-to-world matrix [right | down | forward | pos] of a camera at pos looking
+    along z: forward = z / |z|, right = up x forward normalised, down = forward x right normalised."""
+    forward = np.asarray(z, dtype=np.float64) / np.linalg.norm(z)
+    right = np.cross(np.asarray(up, dtype=np.float64), forward)
+    right = right / np.linalg.norm(right)
+    down = np.cross(forward, right)
+    down = down / np.linalg.norm(down)
+    return np.stack([right, down, forward, np.asarray(pos, dtype=np.float64)], axis=1)
+
+
+def check_proj(points, W, H, fx, fy, cx, cy, c2w):
+    """eval_recon.py:59-85 on the host, step by step in the reference's precisions: True when a point of points [N,3]
+    projects into the view.  The float64 c2w has its columns 1 and 2 negated and is inverted; then in float32
+    c = w2c [p, 1], c.x *= -1, (a, b, zz) = K c, z = zz + 1e-5, (u, v) = (a, b) / z; in view when 0 <= -z, 0 < u < W,
+    0 < v < H.  ops.views_see_points is the same test for a batch of views on the GPU."""
+    c2w = np.array(c2w, dtype=np.float64)
+    c2w[:3, 1] *= -1.0
+    c2w[:3, 2] *= -1.0
+    w2c = np.linalg.inv(c2w).astype(np.float32)
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    homo = np.concatenate([pts, np.ones_like(pts[:, :1])], axis=1).reshape(-1, 4, 1)
+    cam = (w2c @ homo)[:, :3]
+    cam[:, 0] *= -1
+    Km = np.array([[fx, .0, cx], [.0, fy, cy], [.0, .0, 1.0]], dtype=np.float32)
+    uv = Km @ cam
+    z = uv[:, -1:] + np.float32(1e-5)
+    uv = (uv[:, :2] / z)[:, :, 0]
+    mask = (0 <= -z[:, 0, 0]) & (uv[:, 0] < W) & (uv[:, 0] > 0) & (uv[:, 1] < H) & (uv[:, 1] > 0)
+    return bool(mask.sum() > 0)
+
+
+def _rot_about(axis, deg):
+    a = np.radians(deg)
+    k = np.asarray(axis, dtype=np.float64)
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(a) * Kx + (1 - np.cos(a)) * Kx @ Kx
+
+
+def box_candidates(cov):
+    """The candidate orientations of get_cam_position, float64 [2 * 3 * BOX_ANGLES, 3, 3] (rows = box axes): for each
+    of the two base frames - the world axes, and the eigenvectors of the vertices' 3x3 covariance `cov` (numpy eigh,
+    ascending eigenvalues) - and each of its three axes, the frame turned about that axis by 0, 1, ..., BOX_ANGLES - 1
+    degrees."""
+    frames = [np.eye(3), np.linalg.eigh(np.asarray(cov, dtype=np.float64))[1].T]
+    out = []
+    for B in frames:
+        for a in range(3):
+            for deg in range(BOX_ANGLES):
+                out.append(B @ _rot_about(B[a], deg).T)
+    return np.stack(out)
+
+
+def get_cam_position(gt_meshfile_or_vertices):
+    """eval_recon.py:116-124: (extents [3], transform [4,4]) of the box views are sampled in: an oriented bounding box of
+    the ground-truth vertices with its axes ordered by ascending extent (trimesh.bounds.oriented_bounds, ordered=True),
+    extents scaled by (0.3, 0.7, 0.7), transform = box-to-world (rotation | centre) with 0.4 added to transform[2, 3].
+    Deviation: trimesh searches the convex hull for the minimum-volume box; here the box is the smallest-volume one of
+    box_candidates(), each evaluated in float64 on the vertices' device (the GPU when there is one) as the min / max of
+    the vertices' projections on its axes; the first of equal volumes wins.  One host sync."""
+    if isinstance(gt_meshfile_or_vertices, str):
+        v = torch.from_numpy(np.ascontiguousarray(read_ply(gt_meshfile_or_vertices)[0]))
+    else:
+        v = torch.as_tensor(gt_meshfile_or_vertices)
+    if not v.is_cuda and torch.cuda.is_available():
+        v = v.to(torch.device("cuda", torch.cuda.current_device()))
+    v = v.detach().to(torch.float64).reshape(-1, 3)
+    if v.shape[0] < 1:
+        raise RuntimeError("get_cam_position: no vertices")
+    mean = v.mean(0)
+    cov = ((v - mean).T @ (v - mean) / v.shape[0]).cpu().numpy()
+    cand = box_candidates(cov)
+    R = torch.from_numpy(cand).to(v.device)
+    lo = torch.empty(len(cand), 3, dtype=torch.float64, device=v.device)
+    hi = torch.empty_like(lo)
+    for k in range(len(cand)):
+        lo[k], hi[k] = (v @ R[k].T).aminmax(dim=0)
+    ext = hi - lo
+    best = int(torch.argmin(ext.prod(dim=1)))            # (argmin returns the first minimum)
+    ext, lo_b = ext[best].cpu().numpy(), lo[best].cpu().numpy()
+    order = np.argsort(ext, kind="stable")
+    axes = cand[best][order]
+    if np.linalg.det(axes) < 0:
+        axes[2] *= -1.0
+    centre = (lo_b + 0.5 * ext) @ cand[best]
+    extents = ext[order].copy()
+    transform = np.eye(4)
+    transform[:3, :3] = axes.T
+    transform[:3, 3] = centre
+    extents[2] *= 0.7
+    extents[1] *= 0.7
+    extents[0] *= 0.3
+    transform[2, 3] += 0.4
+    return extents, transform
+
+
+def sample_views(extents, transform, n, pc_unseen=None, seed=0, K=(FOCAL, FOCAL, IMG_CX, IMG_CY), H=IMG_H, W=IMG_W):
+    """eval_recon.py:156-175: n camera-to-world matrices, float64 [n,4,4]; per candidate the origin uniform in the box
+    (trimesh.sample.volume_rectangular: transform [(u - 0.5) extents, 1]), the target uniform in +-10000 rounded to 2
+    decimals, up = [0, 0, -1], c2w = viewmatrix(target - origin, up, origin); a candidate is dropped when it sees a point
+    of pc_unseen (check_proj).  Candidates are drawn VIEW_BATCH at a time - six uniforms each, row by row, so the sequence
+    does not depend on the batch size - and tested by one ops.views_see_points call per batch; the first n accepted are
+    kept in draw order.  pc_unseen=None accepts every candidate.  Deviation: a numpy Generator seeded with `seed` instead
+    of `random` and numpy's global state.  Returns (c2ws, {'drawn': candidates tested, 'rejected': dropped among them})."""
+    rng = np.random.default_rng(int(seed))
+    extents, transform = np.asarray(extents, dtype=np.float64), np.asarray(transform, dtype=np.float64)
+    up = np.array([0.0, 0.0, -1.0])
+    pts = None
+    if pc_unseen is not None:
+        pts = _points(pc_unseen)
+        if pts.shape[0] == 0:
+            pts = None
+    kept, drawn, rejected = [], 0, 0
+    while len(kept) < n:
+        u = rng.uniform(size=(VIEW_BATCH, 6))
+        c2ws = np.tile(np.eye(4), (VIEW_BATCH, 1, 1))
+        for k in range(VIEW_BATCH):
+            origin = transform[:3, :3] @ ((u[k, :3] - 0.5) * extents) + transform[:3, 3]
+            target = np.round(-10000.0 + 20000.0 * u[k, 3:], 2)
+            c2ws[k, :3, :] = viewmatrix(target - origin, up, origin)
+        ok = np.ones(VIEW_BATCH, dtype=bool)
+        if pts is not None:
+            ok = ~ops.views_see_points(pts, c2ws, K, H, W).cpu().numpy()
+        for k in range(VIEW_BATCH):
+            if len(kept) == n:
+                break
+            drawn += 1
+            if ok[k]:
+                kept.append(c2ws[k])
+            else:
+                rejected += 1
+        if drawn >= 1000 * max(n, 1) and not kept:
+            raise RuntimeError("sample_views: every one of %d candidate views sees an unseen point" % drawn)
+    return np.stack(kept) if kept else np.zeros((0, 4, 4)), {"drawn": drawn, "rejected": rejected}
+
+
+def depth_l1_metric(rec_v, rec_f, gt_v, gt_f, pc_unseen=None, align=True, n_imgs=1000, seed=0, views=None, chunk=32,
+                    device=None):
+    """In-memory calc_2d_metric: both meshes (vertices [V,3], faces [F,3]; numpy or torch) rendered from n_imgs views
+    of 500 x 500 pixels, focal 300, principal point 249.5 (eval_recon.py:132-138), `chunk` views at a time; only the
+    per-view sums of |gt depth - rec depth| come to the host.  views: an explicit [n,4,4] stack of c2w that bypasses
+    the sampling (get_cam_position on the ground truth, sample_views with pc_unseen and seed).  align: the reconstruction
+    is first moved by the ICP transform.  Returns {'depth_l1': the mean over views and pixels in cm, 'per_view': float64
+    [n] in cm, 'views': the c2w used, 'drawn', 'rejected': sample_views' counters}."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    rec = torch.as_tensor(rec_v).to(dev, torch.float64).reshape(-1, 3)
+    gt = torch.as_tensor(gt_v).to(dev, torch.float64).reshape(-1, 3)
+    rec_f = torch.as_tensor(rec_f).to(dev, torch.int32).reshape(-1, 3)
+    gt_f = torch.as_tensor(gt_f).to(dev, torch.int32).reshape(-1, 3)
+    if align:
+        rec = _transform(icp(rec, gt)[0], rec)
+    info = {"drawn": 0, "rejected": 0}
+    if views is None:
+        extents, transform = get_cam_position(gt)
+        views, info = sample_views(extents, transform, n_imgs, pc_unseen, seed)
+    views = np.asarray(torch.as_tensor(views).detach().cpu().numpy(), dtype=np.float64).reshape(-1, 4, 4)
+    rec32, gt32 = rec.float().contiguous(), gt.float().contiguous()
+    K = (FOCAL, FOCAL, IMG_CX, IMG_CY)
+    sums = []
+    for lo in range(0, len(views), chunk):
+        c = views[lo:lo + chunk]
+        gt_depth = ops.render_mesh_depth(gt32, gt_f, c, K, IMG_H, IMG_W, Z_NEAR, Z_FAR, chunk)
+        rec_depth = ops.render_mesh_depth(rec32, rec_f, c, K, IMG_H, IMG_W, Z_NEAR, Z_FAR, chunk)
+        sums.append(ops.depth_l1(gt_depth, rec_depth))
+    per_view = (torch.cat(sums).cpu().numpy() if sums else np.zeros(0)) / (IMG_H * IMG_W) * 100     # from m to cm
+    return {"depth_l1": float(per_view.mean()) if len(per_view) else float("nan"), "per_view": per_view, "views": views,
+            "drawn": info["drawn"], "rejected": info["rejected"]}
+
+
 def calc_2d_metric(rec_meshfile, gt_meshfile, align=True, n_imgs=1000):
-    raise NotImplementedError("the 2D depth-L1 metric (reference eval_recon.py:127+) needs a mesh rasteriser, "
-                              "which this project does not have")
+    """eval_recon.py:127-207: the depth L1 (cm) between renders of the ground-truth mesh and of the reconstruction from
+    n_imgs random views inside the room that see none of the points of GT_pc_unseen.npy (the file beside the
+    ground-truth mesh, '_culled.ply' replaced by '_pc_unseen.npy'; missing = the error of np.load, as in the reference);
+    printed as the reference prints it and returned as depth_l1_metric's dict."""
+    rec_v, rec_f, _ = read_ply(rec_meshfile)
+    gt_v, gt_f, _ = read_ply(gt_meshfile)
+    unseen_gt_pointcloud_file = gt_meshfile.replace('_culled.ply', '_pc_unseen.npy')
+    pc_unseen = np.load(unseen_gt_pointcloud_file)
+    rec_v = torch.as_tensor(rec_v).to(torch.float64)
+    if align:
+        T = get_align_transformation(rec_meshfile, gt_meshfile)
+        rec_v = rec_v @ torch.from_numpy(T[:3, :3].T.copy()) + torch.from_numpy(T[:3, 3].copy())
+    r = depth_l1_metric(rec_v, rec_f, gt_v, gt_f, pc_unseen=pc_unseen, align=False, n_imgs=n_imgs)
+    print('Depth L1: ', r["depth_l1"])
+    return r
 
 
 if __name__ == '__main__':
