@@ -5,6 +5,10 @@ float16 copies and refreshes all 12 in one launch (eslam_planes_to_half) after a
 `ops.mixed_precision(half)` the renderer's kernels gather texels from the copies (float32 accumulation), run both decoders on
 bf16 MFMA with float32 accumulation - in the backward pass too - and accumulate plane gradients in float32 for the masters.
 Sampling (z_vals), the loss, the composite and its backward, the scatter and the optimiser are the float32 path.
+
+The copies are the IEEE round-to-nearest-even conversion of the masters, half subnormals included; a master beyond the half
+range (|x| >= 65520) becomes +-inf in its copy and stays inf - nothing clamps it.  A copy is as old as its last refresh: an
+optimiser step changes the masters only.
 """
 import ctypes
 
