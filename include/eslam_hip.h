@@ -50,8 +50,10 @@ typedef struct {
                                (stride_c = 1, stride_x = 32: 64-byte texels).  When all 12 planes carry one, eslam_render_fwd*,
                                eslam_render_bwd* run the mixed-precision path of BASELINE.json configs[4]: texels gathered from
                                the half copies (float32 accumulation), decoders on bf16 MFMA forward AND backward, plane
-                               gradients accumulated in float32 into `grad` (the float32 master's gradient).  The saved
-                               features `feat` then hold R*S*128 bf16 values (half the bytes of the float32 path's buffer). */
+                               gradients accumulated in float32 into `grad` (the float32 master's gradient), ray gradients
+                               (g_rays_o / g_rays_d) from the bilinear derivative on the half texels.  The saved
+                               features `feat` then hold R*S*128 bf16 values (half the bytes of the float32 path's buffer).
+                               The free-point entries are float32 only: eslam_decode_bwd refuses planes that carry it.   */
 } eslam_plane_t;
 
 typedef struct {            /* src/networks/decoders.py:47-60                                      */
@@ -201,6 +203,8 @@ int64_t eslam_bwd_workspace_bytes(int64_t n_points);
  * non-NULL overwrites them ([R,3] each) with the gradient through pts = o + d z.  z_vals carries no gradient
  * (Renderer.py builds it under no_grad / from gt_depth).  ray_order: the buffer eslam_ray_order filled, or NULL
  * (then the order is computed here).
+ * Mixed precision (planes with data_f16): the same outputs, g_rays_o / g_rays_d included - the position gradient is taken
+ * on the half copies, behind the scatter, or behind the decoder backward alone when no plane takes a gradient (tracking).
  * workspace: eslam_bwd_workspace_bytes(R*S) bytes.                                                          */
 int eslam_render_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                      const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
@@ -215,7 +219,8 @@ int eslam_render_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, c
  * composite backward and decoder backward are one launch.  depth [R], rgb [R,3]: the forward outputs.  upstream [1] on
  * the device = d L / d loss (NULL = 1).  loss_out [1] (optional): receives the loss value formed from acc (a ray-sharded
  * caller's acc is only complete after its all-reduce).  g_depth / g_rgb / g_sdf (each optional): FURTHER upstream
- * gradients on the rendered outputs, added to the loss's own.  Everything else as eslam_render_bwd.                */
+ * gradients on the rendered outputs, added to the loss's own.  Everything else as eslam_render_bwd, the ray gradients
+ * of the mixed-precision path included.                                                                            */
 int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                           const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
                           const float* sdf, const float* raw_rgb, const float* feat, const float* depth,
@@ -375,7 +380,8 @@ int eslam_views_see_points(const float* points, int64_t n_points, const float* w
                            float cx, float cy, int H, int W, uint8_t* seen, eslam_stream_t stream);
 
 /* Backward of eslam_decode_fwd: g_raw [N,4] upstream, raw [N,4] the forward output.  Same gradient outputs as
- * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.                          */
+ * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.  float32 planes only: planes that carry
+ * data_f16 are refused (the free-point backward of the mixed-precision path is not built).              */
 int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                      const float* pts, int64_t N, const float* raw, const float* feat, const float* g_raw,
                      float* g_dec, float* g_pts, void* workspace, eslam_stream_t stream);

@@ -6,6 +6,7 @@
 //   dec_grad_reduce_kernel slabs -> flat decoder gradient
 //   scatter (eslam_scatter.hip)  g_feat -> plane gradients
 //   coord_bwd_kernel       optional: gradient w.r.t. the sample position -> rays_o / rays_d (pose) or points
+//   coord_bwd_lowp_kernel  the same for the rays of the mixed-precision path, on the planes' half copies
 #include <stdlib.h>
 #include "eslam_decode_tile.h"
 #include "eslam_loss_final.h"
@@ -729,6 +730,100 @@ __global__ __launch_bounds__(256, 2) void coord_bwd_kernel(const PlaneSet planes
     }
 }
 
+// Mixed precision: the same gradient on the planes' half copies.  What the forward pass interpolated ARE the fp16-rounded
+// texels (gather8_half), so the derivative of the bilinear form acts on them, not on the float32 masters; the roundings of
+// planes and features pass gradients through.  Gather role of the mixed-precision tile: piece g = channels 8g..8g+7 of a
+// level, one 16-byte load per corner (a quad of lanes one 64-byte texel).  Arithmetic, gates and factors are coord_grad8's.
+__device__ __forceinline__ void coord_grad8_half(const eslam_plane_t& P, float u, float v, int g, const float gf[8],
+                                                 float& gu, float& gv) {
+    const AxisCoord ax = axis_coord(u, P.w);
+    const AxisCoord ay = axis_coord(v, P.h);
+    const unsigned sy = (unsigned)P.stride_y, sx = (unsigned)P.stride_x;
+    const unsigned r0 = ay.i0 * sy, r1 = ay.i1 * sy, c0 = ax.i0 * sx, c1 = ax.i1 * sx, g8 = 8u * g;
+    const _Float16* __restrict__ data = (const _Float16*)P.data_f16;
+    const half8_t t00 = *(const half8_t*)(data + r0 + c0 + g8);
+    const half8_t t01 = *(const half8_t*)(data + r0 + c1 + g8);
+    const half8_t t10 = *(const half8_t*)(data + r1 + c0 + g8);
+    const half8_t t11 = *(const half8_t*)(data + r1 + c1 + g8);
+    float su = 0.f, sv = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float a00 = (float)t00[i], a01 = (float)t01[i], a10 = (float)t10[i], a11 = (float)t11[i];
+        su += gf[i] * ((a01 - a00) * (1.0f - ay.t) + (a11 - a10) * ay.t);
+        sv += gf[i] * ((a10 - a00) * (1.0f - ax.t) + (a11 - a01) * ax.t);
+    }
+    gu += ax.inside ? su * (0.5f * (float)(P.w - 1)) : 0.0f;
+    gv += ay.inside ? sv * (0.5f * (float)(P.h - 1)) : 0.0f;
+}
+
+// One wave per ray (the RENDER mode of coord_bwd_kernel), 48 texel loads per sample where the float32 kernel issues 96.
+// g_feat stays float32 in natural channel order (written by the LOWP mlp_bwd_kernel for the scatter): the lane's 8
+// channels of a level are two adjacent 16-byte loads.  No LDS.  165 VGPRs, 3 waves per SIMD (as the float32 kernel, 152):
+// asked for 4 waves (128 VGPRs) the compiler spills 27 registers to scratch inside the sample loop, so 3 is what is asked.
+__global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet planes, const Bound bnd,
+                                                                const float* __restrict__ rays_o,
+                                                                const float* __restrict__ rays_d,
+                                                                const float* __restrict__ z_vals, int R, int S,
+                                                                const float* __restrict__ g_feat,
+                                                                float* __restrict__ g_rays_o, float* __restrict__ g_rays_d) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane >> 2, g = lane & 3;                 // gather role of the mixed-precision tile
+    const int64_t ray = (int64_t)blockIdx.x * 4 + wave;
+    if (ray >= R) return;
+    const float ox = rays_o[ray * 3 + 0], oy = rays_o[ray * 3 + 1], oz = rays_o[ray * 3 + 2];
+    const float dx = rays_d[ray * 3 + 0], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
+    const int64_t base = ray * S;
+    const float sc3[3] = {2.0f / (bnd.hi[0] - bnd.lo[0]), 2.0f / (bnd.hi[1] - bnd.lo[1]), 2.0f / (bnd.hi[2] - bnd.lo[2])};
+    float go_acc[3] = {0.f, 0.f, 0.f}, gd_acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int s0 = 0; s0 < S; s0 += 16) {
+        const int oz0 = opaque_zero(s0);      // keeps the 12 planes' scalar loads inside this loop (see gather_features)
+        const int s = s0 + r;
+        const bool valid = s < S;
+        const int sc_ = min(s, S - 1);
+        const float zz = z_vals[base + sc_];
+        const float x = norm_coord(ox + dx * zz, bnd.lo[0], bnd.hi[0]);
+        const float y = norm_coord(oy + dy * zz, bnd.lo[1], bnd.hi[1]);
+        const float z = norm_coord(oz + dz * zz, bnd.lo[2], bnd.hi[2]);
+        float gp[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+#pragma unroll
+            for (int lvl = 0; lvl < 2; ++lvl) {
+                const float* gfp = g_feat + (base + sc_) * 128 + d * 64 + lvl * 32 + 8 * g;
+                const float4_t ga = *(const float4_t*)gfp, gb = *(const float4_t*)(gfp + 4);
+                const float gf[8] = {ga[0], ga[1], ga[2], ga[3], gb[0], gb[1], gb[2], gb[3]};
+#pragma unroll
+                for (int o = 0; o < 3; ++o) {
+                    const eslam_plane_t& P = planes.p[2 * (3 * d + o) + lvl + oz0];
+                    float gu = 0.f, gv = 0.f;
+                    coord_grad8_half(P, ORIENT_U(o, x, y, z), ORIENT_V(o, x, y, z), g, gf, gu, gv);
+                    __builtin_amdgcn_sched_barrier(0);
+                    gp[o == 2 ? 1 : 0] += gu;      // first coordinate: x (xy, xz) or y (yz)
+                    gp[o == 0 ? 1 : 2] += gv;      // second coordinate: y (xy) or z (xz, yz)
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float v = gp[k];
+            v += __shfl_xor(v, 1, WAVE);            // sum the four pieces of the point
+            v += __shfl_xor(v, 2, WAVE);
+            v = valid ? v * sc3[k] : 0.0f;
+            if (g == 0) { go_acc[k] += v; gd_acc[k] += v * zz; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float a = wave_sum(go_acc[k]);
+        const float b = wave_sum(gd_acc[k]);
+        if (lane == 0) {
+            g_rays_o[ray * 3 + k] = a;
+            g_rays_d[ray * 3 + k] = b;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
@@ -796,8 +891,8 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     const int lowp = eslam_planes_lowp(planes);
     if (lowp < 0) return 1;
     if (lowp) {
-        if (mode == 0 || g_out_a) {
-            eslam_set_error("mixed precision: only the ray backward to planes and decoders is built (no point / pose gradients)");
+        if (mode == 0) {
+            eslam_set_error("mixed precision: the backward of free points (eslam_decode_bwd: decoders, planes, point gradients) is not built");
             return 1;
         }
         if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, true); else LAUNCH_MB(1, false, true); }
@@ -850,7 +945,10 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     hipLaunchKernelGGL((coord_bwd_kernel<CLv, RD>), grid, block, 0, st, ps, bnd, rays_o, rays_d, z_or_pts, (int)R, \
                        S, g_feat, g_out_a, g_out_b)
         eslam_prof_begin(PROF_COORD_BWD, st);
-        if (cl && render) LAUNCH(true, true);
+        if (lowp)       // (render mode, channels-last half copies: checked above and by eslam_planes_lowp)
+            hipLaunchKernelGGL(coord_bwd_lowp_kernel, grid, block, 0, st, ps, bnd, rays_o, rays_d, z_or_pts, (int)R, S, g_feat,
+                               g_out_a, g_out_b);
+        else if (cl && render) LAUNCH(true, true);
         else if (cl) LAUNCH(true, false);
         else if (render) LAUNCH(false, true);
         else LAUNCH(false, false);

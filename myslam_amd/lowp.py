@@ -6,6 +6,12 @@ float16 copies and refreshes all 12 in one launch (eslam_planes_to_half) after a
 bf16 MFMA with float32 accumulation - in the backward pass too - and accumulate plane gradients in float32 for the masters.
 Sampling (z_vals), the loss, the composite and its backward, the scatter and the optimiser are the float32 path.
 
+Pose gradients: under `ops.mixed_precision(half, ray_grads=True)` rays that require grad get g_rays_o / g_rays_d from the half
+copies too (coord_bwd_lowp_kernel: the bilinear derivative acts on the fp16-rounded texels the forward pass interpolated),
+with the separate losses and with render_batch_ray_with_loss - so the path can track and run the joint mapping iteration
+(slam.SlamConfig.mixed_precision).  Without ray_grads such rays raise, as they always did.
+Still not built: ops.DecodeFn / Decoders.forward on the copies and gradients with respect to free points (eslam_decode_*).
+
 The copies are the IEEE round-to-nearest-even conversion of the masters, half subnormals included; a master beyond the half
 range (|x| >= 65520) becomes +-inf in its copy and stays inf - nothing clamps it.  A copy is as old as its last refresh: an
 optimiser step changes the masters only.

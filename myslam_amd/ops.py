@@ -393,25 +393,31 @@ def current_fused_loss():
 
 
 _half_planes = None
+_half_ray_grads = False
 
 
 class mixed_precision:
     """Context manager: Renderer.render_batch_ray calls issued inside run the mixed-precision kernels (BASELINE.json
     configs[4]: texels gathered from float16 copies of the planes, decoders on bf16 MFMA forward and backward, float32
     accumulation everywhere, plane gradients accumulated in float32 for the float32 masters).  half: a lowp.HalfPlanes (or any
-    object with `.flat`, the 12 float16 channels_last copies in all_planes order) - refresh it after every optimiser step."""
+    object with `.flat`, the 12 float16 channels_last copies in all_planes order) - refresh it after every optimiser step.
+    ray_grads=True: rays that require grad (pose optimisation: tracking, joint mapping) get their gradients from the half
+    copies as well (coord_bwd_lowp_kernel) - the derivative of what the forward pass interpolated.  The default refuses such
+    rays, as before this was built: a caller that did not ask keeps its error."""
 
-    def __init__(self, half):
+    def __init__(self, half, ray_grads=False):
         self.half = half
+        self.ray_grads = bool(ray_grads)
 
     def __enter__(self):
-        global _half_planes
-        self._prev, _half_planes = _half_planes, self.half
+        global _half_planes, _half_ray_grads
+        self._prev, _half_planes = (_half_planes, _half_ray_grads), self.half
+        _half_ray_grads = self.ray_grads
         return self.half
 
     def __exit__(self, *a):
-        global _half_planes
-        _half_planes = self._prev
+        global _half_planes, _half_ray_grads
+        _half_planes, _half_ray_grads = self._prev
 
 
 def join_ray_order(device):
@@ -579,8 +585,9 @@ class RenderFn(torch.autograd.Function):
         arr, _ = _hip.make_planes(planes, half=half)
         dec, keep = _hip.make_decoders(params, beta)
         needs = any(ctx.needs_input_grad)
-        if half is not None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-            raise RuntimeError("mixed precision: gradients with respect to the rays (pose) are not built; detach the rays")
+        if half is not None and not _half_ray_grads and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            raise RuntimeError("mixed precision: gradients with respect to the rays (pose) are off; ask for them with "
+                               "ops.mixed_precision(half, ray_grads=True) or detach the rays")
         depth = torch.empty(R, device=dev)
         rgb = torch.empty(R, 3, device=dev)
         sdf = torch.empty(R, S, device=dev)

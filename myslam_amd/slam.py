@@ -21,6 +21,8 @@ render quality at equal iterations.
 from dataclasses import dataclass
 from types import SimpleNamespace
 
+import contextlib
+
 import torch
 
 
@@ -49,6 +51,9 @@ class SlamConfig:
     planes_lr: float = 0.005
     c_planes_lr: float = 0.005
     mapping_w: tuple = (5.0, 200.0, 10.0, 0.1, 5.0)
+    # BASELINE.json configs[4]: tracking, mapping and evaluation render on float16 copies of the planes with bf16-MFMA
+    # decoders (lowp.py); the float32 planes stay the optimiser's masters.  Needs a backend with the two hooks below.
+    mixed_precision: bool = False
 
 
 class HipBackend:
@@ -87,6 +92,17 @@ class HipBackend:
     def keyframe_selection_overlap(self, ns, gt_color, gt_depth, c2w, num):
         return self._kf_select(ns, gt_color, gt_depth, c2w, num)
 
+    # SlamConfig.mixed_precision: the two hooks a backend needs for it
+    def half_planes(self, all_planes):
+        """float16 copies of the planes (an object with .refresh(all_planes))."""
+        from . import lowp
+        return lowp.HalfPlanes(all_planes)
+
+    def mixed_precision(self, half):
+        """Context manager: render calls inside run on the copies, pose gradients included."""
+        from . import ops
+        return ops.mixed_precision(half, ray_grads=True)
+
 
 class Slam:
     def __init__(self, sc, cfg=None, device="cuda:0", backend=None, seed=0):
@@ -95,6 +111,9 @@ class Slam:
         self.device = torch.device(device)
         self.be = backend or HipBackend(sc, device)
         self.truncation = sc.truncation
+        if self.cfg.mixed_precision and not all(callable(getattr(self.be, h, None)) for h in ("half_planes", "mixed_precision")):
+            raise ValueError(f"SlamConfig.mixed_precision: the backend {type(self.be).__name__} does not support mixed precision "
+                             "(it has no half_planes / mixed_precision hooks)")
         gen = torch.Generator().manual_seed(seed)
         # ESLAM.py:201-210: planes ~ N(0, 0.01^2); same values for every backend (drawn on the CPU)
         planes = []
@@ -105,6 +124,8 @@ class Slam:
                 lvl.append(t.to(self.device).contiguous(memory_format=torch.channels_last))
             planes.append(lvl)
         self.all_planes = tuple(planes)
+        # one set of half copies for the whole run; refreshed after every mapping step (tracking changes no plane)
+        self.half = self.be.half_planes(self.all_planes) if self.cfg.mixed_precision else None
         torch.manual_seed(seed)
         self.decoders = self.be.Decoders(learnable_beta=sc.learnable_beta).to(self.device)
         self.decoders.bound = sc.bound
@@ -115,6 +136,10 @@ class Slam:
         self.stats = dict(tracking_iters=0, mapping_iters=0, tracking_rays=0, mapping_rays=0)
 
     # ------------------------------------------------------------------------------------------------------------
+    def _precision(self):
+        """The context render calls run in: the backend's mixed-precision one over self.half, or nothing."""
+        return contextlib.nullcontext() if self.half is None else self.be.mixed_precision(self.half)
+
     def _prefilter(self, ro, rd, gd, gc, need_depth):
         """Mapper.py:322-332 / Tracker.py:175-187: drop rays whose depth lies beyond the scene bound."""
         with torch.no_grad():
@@ -147,7 +172,8 @@ class Slam:
                                             sc.W - cfg.ignore_edge_W, cfg.tracking_pixels, sc.H, sc.W, sc.fx, sc.fy,
                                             sc.cx, sc.cy, c2w, gt_depth[None], gt_color[None], self.device)
             ro, rd, gd, gc = self._prefilter(ro, rd, gd, gc, need_depth=True)
-            depth, color, sdf, z = be.render_batch_ray(planes, self.decoders, rd, ro, self.truncation, gd)
+            with self._precision():
+                depth, color, sdf, z = be.render_batch_ray(planes, self.decoders, rd, ro, self.truncation, gd)
             loss = be.tracking_loss(depth, color, sdf, z, gd, gc, self.truncation, cfg.tracking_w)
             opt.zero_grad()
             loss.backward()
@@ -204,11 +230,14 @@ class Slam:
             ro, rd, gd, gc = be.get_samples(0, sc.H, 0, sc.W, pixs, sc.H, sc.W, sc.fx, sc.fy, sc.cx, sc.cy, c2ws_, gds,
                                             gcs, self.device)
             ro, rd, gd, gc = self._prefilter(ro, rd, gd, gc, need_depth=False)
-            depth, color, sdf, z = be.render_batch_ray(self.all_planes, self.decoders, rd, ro, self.truncation, gd)
+            with self._precision():
+                depth, color, sdf, z = be.render_batch_ray(self.all_planes, self.decoders, rd, ro, self.truncation, gd)
             loss = be.mapping_loss(depth, color, sdf, z, gd, gc, self.truncation, cfg.mapping_w)
             opt.zero_grad()
             loss.backward()
             opt.step()
+            if self.half is not None:
+                self.half.refresh(self.all_planes)      # (the Parameters re-wrapped above share the planes' storage)
             self.stats["mapping_iters"] += 1
             self.stats["mapping_rays"] += int(gd.shape[0])
         if joint:                                                                      # Mapper.py:352-363
@@ -247,7 +276,7 @@ class Slam:
     # ------------------------------------------------------------------------------------------------------------
     def render_quality(self, gt_color, gt_depth, c2w):
         """PSNR (dB) of the rendered colour and L1 (length units) of the rendered depth against a frame."""
-        with torch.no_grad():
+        with torch.no_grad(), self._precision():      # the field that is evaluated is the one that was trained
             depth, color = self.be.render_img(self.all_planes, self.decoders, c2w, self.truncation, gt_depth)
         valid = gt_depth > 0
         l1 = float((depth.float() - gt_depth)[valid].abs().mean())

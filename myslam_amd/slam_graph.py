@@ -37,6 +37,10 @@ class GraphedSlam(Slam):
     def __init__(self, sc, cfg=None, device="cuda:0", seed=0, warmup=2, use_graphs=True):
         """use_graphs=False keeps the sync-free iterations (masks, device-side median / best pose, in-place optimiser
         reset) but issues them eagerly - for hosts that cannot capture graphs; about 2x the plain eager loop."""
+        if cfg is not None and cfg.mixed_precision:
+            # the captured iterations draw their samples with the in-kernel generator (the compiled render call), which the
+            # mixed-precision path does not use (ops.ext_render_ok): capturing it is not built
+            raise NotImplementedError("GraphedSlam: SlamConfig.mixed_precision is not built for the graph-captured loop; use slam.Slam")
         super().__init__(sc, cfg, device, backend=HipBackend(sc, device), seed=seed)
         self.warmup = warmup
         self.use_graphs = bool(use_graphs)

@@ -1,5 +1,5 @@
 """Timings of the other callers of the path on the GPU box (not the headline metric): tracking iteration (pose gradients
-only), whole-image render (render_img, Frame_Visualizer's caller), dense field query (Mesher.eval_points' caller)."""
+only; float32 and mixed precision), the mixed-precision mapping step with and without pose gradients, whole-image render (render_img, Frame_Visualizer's caller), dense field query (Mesher.eval_points' caller)."""
 import ctypes, sys, time, torch
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 from myslam_amd import harness, losses, _hip
@@ -25,6 +25,34 @@ print(f"tracking iteration {wl.R} rays x {wl.S}: eager {timed(track):.3f} ms, gr
 buf = (ctypes.c_float * 12)(); lib.eslam_profile_enable(1); track(); torch.cuda.synchronize(); lib.eslam_profile_read(buf); lib.eslam_profile_enable(0)
 print('  kernels ms:', {lib.eslam_profile_name(i).decode(): round(buf[i], 4) for i in range(12) if buf[i] >= 0})
 
+# the same tracking iteration on the mixed-precision path: fp16 plane copies, LOWP decoder backward without weight gradients,
+# pose gradients from the copies (coord_bwd_lowp_kernel)
+from myslam_amd import lowp, ops
+half = lowp.HalfPlanes(wl.planes)
+def track_lp():
+    with ops.mixed_precision(half, ray_grads=True):
+        track()
+gl = harness.GraphedStep(track_lp, [wl.rays_o, wl.rays_d])
+print(f"tracking iteration {wl.R} rays x {wl.S}, mixed precision: eager {timed(track_lp):.3f} ms, graph replay {timed(gl):.3f} ms")
+lib.eslam_profile_enable(1); track_lp(); torch.cuda.synchronize(); lib.eslam_profile_read(buf); lib.eslam_profile_enable(0)
+print('  kernels ms:', {lib.eslam_profile_name(i).decode(): round(buf[i], 4) for i in range(12) if buf[i] >= 0})
+del g, gl
+
+# the mixed-precision mapping step at 4096 x 64 with pose gradients off and on: the cost of the extra kernel on the joint iteration
+for rg in (False, True):
+    wm = harness.make_workload('room0', 4096, 56, 8, device=dev, rays_grad=rg)
+    hm = lowp.HalfPlanes(wm.planes)
+    def map_lp():
+        wm.rays_o.grad = None; wm.rays_d.grad = None
+        with ops.mixed_precision(hm, ray_grads=rg):
+            return wm.step()
+    gm = harness.GraphedStep(map_lp, wm.params() + [wm.rays_o, wm.rays_d])
+    t = timed(gm, n=50)
+    lib.eslam_profile_enable(1); map_lp(); torch.cuda.synchronize(); lib.eslam_profile_read(buf); lib.eslam_profile_enable(0)
+    print(f"mapping step {wm.R} x {wm.S}, mixed precision, pose gradients {'on' if rg else 'off'}: graph replay {t:.3f} ms")
+    print('  kernels ms:', {lib.eslam_profile_name(i).decode(): round(buf[i], 4) for i in range(12) if buf[i] >= 0})
+    del gm, wm, hm
+
 # render_img: full Replica image 680 x 1200 = 816000 rays x 40 samples, no grad
 r = wl.renderer
 gt = torch.full((r.H, r.W), 1.5, device=dev)
@@ -44,7 +72,6 @@ with torch.no_grad():
 print(f"Decoders.forward 500k points: {t:.3f} ms  ({500000/t*1e3:.3e} points/s)")
 
 # mixed precision forward (configs[4]) vs float32 forward, inference, 4096 x 64 and a whole image in one chunk
-from myslam_amd import lowp
 wl2 = harness.make_workload('room0', 4096, 56, 8, device=dev)
 ph = lowp.half_planes(wl2.planes)
 rand = wl2._rand

@@ -65,6 +65,28 @@ for name, scene, R, ns, ni, zf in (("room0_4096x64", "room0", 4096, 56, 8, 0.0),
         row["lowp_rs_per_s"] = wl.R * wl.S / row["lowp_graph_ms"] * 1e3
         row["lowp_refresh_ms"] = round(timed(lambda: half.refresh(wl.planes)), 4)
         del gl
+    if name == "room0_4096x64":
+        # the tracking iteration (2000 x 40, decoders frozen, planes detached, pose gradients only) on float32 and on the
+        # mixed-precision path: per kernel, and replayed
+        from myslam_amd import losses, lowp, ops
+        wt = harness.make_workload(scene, 2000, 32, 8, device=dev, rays_grad=True)
+        tp = tuple([p.detach() for p in grp] for grp in wt.planes)
+        for p in wt.decoders.parameters(): p.requires_grad_(False)
+        th = lowp.HalfPlanes(wt.planes)
+        def track():
+            wt.rays_o.grad = None; wt.rays_d.grad = None
+            d, c, s, z = wt.renderer.render_batch_ray(tp, wt.decoders, wt.rays_d, wt.rays_o, dev, wt.truncation, gt_depth=wt.gt_depth)
+            losses.tracking_loss(d, c, s, z, wt.gt_depth, wt.gt_color, wt.truncation).backward()
+        def track_lp():
+            with ops.mixed_precision(th, ray_grads=True):
+                track()
+        for key, fn in (("tracking", track), ("tracking_lowp", track_lp)):
+            for _ in range(5): fn()
+            row[key + "_kernels_us"] = kernel_profile(fn)
+            gt_ = harness.GraphedStep(fn, [wt.rays_o, wt.rays_d])
+            row[key + "_graph_ms"] = round(timed(gt_), 4)
+            del gt_
+        del wt, tp, th
     print(json.dumps(row), flush=True)
     del wl
     torch.cuda.empty_cache()
