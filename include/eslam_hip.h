@@ -53,7 +53,10 @@ typedef struct {
                                gradients accumulated in float32 into `grad` (the float32 master's gradient), ray gradients
                                (g_rays_o / g_rays_d) from the bilinear derivative on the half texels.  The saved
                                features `feat` then hold R*S*128 bf16 values (half the bytes of the float32 path's buffer).
-                               The free-point entries are float32 only: eslam_decode_bwd refuses planes that carry it.   */
+                               The free-point entries dispatch on it in the same way: eslam_decode_fwd (all three variants;
+                               feat then [N,128] bf16), eslam_sdf_grid and eslam_decode_bwd (plane, decoder and point
+                               gradients; g_pts from the bilinear derivative on the half texels).  In SDF-only mode the six
+                               geometry planes decide.  All 12 planes carry a copy or none does.                        */
 } eslam_plane_t;
 
 typedef struct {            /* src/networks/decoders.py:47-60                                      */
@@ -380,8 +383,9 @@ int eslam_views_see_points(const float* points, int64_t n_points, const float* w
                            float cx, float cy, int H, int W, uint8_t* seen, eslam_stream_t stream);
 
 /* Backward of eslam_decode_fwd: g_raw [N,4] upstream, raw [N,4] the forward output.  Same gradient outputs as
- * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.  float32 planes only: planes that carry
- * data_f16 are refused (the free-point backward of the mixed-precision path is not built).              */
+ * eslam_render_bwd, with g_pts [N,3] (may be NULL) instead of ray gradients.  Planes that carry data_f16: the mixed-precision
+ * path, as in eslam_render_bwd - feat is what eslam_decode_fwd saved on the same planes ([N,128] bf16), g_pts is taken on the
+ * half copies, plane gradients accumulate in float32 into `grad`.                                          */
 int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                      const float* pts, int64_t N, const float* raw, const float* feat, const float* g_raw,
                      float* g_dec, float* g_pts, void* workspace, eslam_stream_t stream);

@@ -6,7 +6,7 @@
 //   dec_grad_reduce_kernel slabs -> flat decoder gradient
 //   scatter (eslam_scatter.hip)  g_feat -> plane gradients
 //   coord_bwd_kernel       optional: gradient w.r.t. the sample position -> rays_o / rays_d (pose) or points
-//   coord_bwd_lowp_kernel  the same for the rays of the mixed-precision path, on the planes' half copies
+//   coord_bwd_lowp_kernel  the same for the rays and the free points of the mixed-precision path, on the planes' half copies
 #include <stdlib.h>
 #include "eslam_decode_tile.h"
 #include "eslam_loss_final.h"
@@ -102,6 +102,9 @@ struct RayBwdIn {                  // MODE >= 1: what the composite backward of 
 // LOWP: the mixed-precision tile (eslam_decode_tile.h): hidden layers recomputed and every product of the backward pass on
 // bf16 MFMA (16x16x32 / 16x16x16) with float32 accumulation - 15 MFMAs of 16 cycles per 16 points and decoder instead of
 // 68 of 32 cycles; features, activations' masks, biases and all accumulators stay float32.
+// MODE 0 with LOWP (free points, eslam_decode_bwd on half copies; saved features bf16): WGRAD 159 VGPRs and 66.6 KB of LDS -
+// two workgroups per CU, i.e. the 2 waves per SIMD of the bound, are what the LDS allows; frozen decoders 90 VGPRs, 15 KB,
+// 5 waves per SIMD (the bound is a floor).  Neither uses scratch.
 template <int MODE, bool WGRAD, bool LOWP>
 __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t dec, const float* __restrict__ feat,
                                                       const float* __restrict__ g_o, int64_t N,
@@ -756,10 +759,14 @@ __device__ __forceinline__ void coord_grad8_half(const eslam_plane_t& P, float u
     gv += ay.inside ? sv * (0.5f * (float)(P.h - 1)) : 0.0f;
 }
 
-// One wave per ray (the RENDER mode of coord_bwd_kernel), 48 texel loads per sample where the float32 kernel issues 96.
+// RENDER: one wave per ray (the RENDER mode of coord_bwd_kernel), 48 texel loads per sample where the float32 kernel issues 96.
+// else:   one wave per 64 free points in four passes of 16, four lanes per point (z_vals = pts [N,3], R = N); g_rays_o =
+//         g_pts [N,3], written directly.
 // g_feat stays float32 in natural channel order (written by the LOWP mlp_bwd_kernel for the scatter): the lane's 8
-// channels of a level are two adjacent 16-byte loads.  No LDS.  165 VGPRs, 3 waves per SIMD (as the float32 kernel, 152):
-// asked for 4 waves (128 VGPRs) the compiler spills 27 registers to scratch inside the sample loop, so 3 is what is asked.
+// channels of a level are two adjacent 16-byte loads.  No LDS.  RENDER: 166 VGPRs, 3 waves per SIMD (as the float32 kernel,
+// 152): asked for 4 waves (128 VGPRs) the compiler spills 27 registers to scratch inside the sample loop, so 3 is what is asked.
+// Points: 152 VGPRs, no scratch, 3 waves per SIMD under the same bound.
+template <bool RENDER>
 __global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet planes, const Bound bnd,
                                                                 const float* __restrict__ rays_o,
                                                                 const float* __restrict__ rays_d,
@@ -768,23 +775,36 @@ __global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet p
                                                                 float* __restrict__ g_rays_o, float* __restrict__ g_rays_d) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane >> 2, g = lane & 3;                 // gather role of the mixed-precision tile
-    const int64_t ray = (int64_t)blockIdx.x * 4 + wave;
-    if (ray >= R) return;
-    const float ox = rays_o[ray * 3 + 0], oy = rays_o[ray * 3 + 1], oz = rays_o[ray * 3 + 2];
-    const float dx = rays_d[ray * 3 + 0], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
-    const int64_t base = ray * S;
+    // points: the wave's index is wave-uniform; say so, so that the trip count and the rows (functions of it, not of S) are
+    // scalar and the loop's branch is a scalar one
+    const int64_t unit = (int64_t)blockIdx.x * 4 + (RENDER ? wave : __builtin_amdgcn_readfirstlane(wave));
+    const int64_t nunits = RENDER ? R : ((int64_t)R + 63) / 64;
+    if (unit >= nunits) return;
+    float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
+    if (RENDER) {
+        ox = rays_o[unit * 3 + 0]; oy = rays_o[unit * 3 + 1]; oz = rays_o[unit * 3 + 2];
+        dx = rays_d[unit * 3 + 0]; dy = rays_d[unit * 3 + 1]; dz = rays_d[unit * 3 + 2];
+    }
+    const int64_t base = RENDER ? unit * S : unit * 64;
+    const int scount = RENDER ? S : (int)min((int64_t)64, (int64_t)R - base);
     const float sc3[3] = {2.0f / (bnd.hi[0] - bnd.lo[0]), 2.0f / (bnd.hi[1] - bnd.lo[1]), 2.0f / (bnd.hi[2] - bnd.lo[2])};
     float go_acc[3] = {0.f, 0.f, 0.f}, gd_acc[3] = {0.f, 0.f, 0.f};
 #pragma unroll 1
-    for (int s0 = 0; s0 < S; s0 += 16) {
+    for (int s0 = 0; s0 < scount; s0 += 16) {
         const int oz0 = opaque_zero(s0);      // keeps the 12 planes' scalar loads inside this loop (see gather_features)
         const int s = s0 + r;
-        const bool valid = s < S;
-        const int sc_ = min(s, S - 1);
-        const float zz = z_vals[base + sc_];
-        const float x = norm_coord(ox + dx * zz, bnd.lo[0], bnd.hi[0]);
-        const float y = norm_coord(oy + dy * zz, bnd.lo[1], bnd.hi[1]);
-        const float z = norm_coord(oz + dz * zz, bnd.lo[2], bnd.hi[2]);
+        const bool valid = s < scount;
+        const int sc_ = min(s, scount - 1);
+        float x, y, z, zz = 0.f;
+        if (RENDER) {
+            zz = z_vals[base + sc_];
+            x = ox + dx * zz; y = oy + dy * zz; z = oz + dz * zz;
+        } else {
+            x = z_vals[(base + sc_) * 3 + 0]; y = z_vals[(base + sc_) * 3 + 1]; z = z_vals[(base + sc_) * 3 + 2];
+        }
+        x = norm_coord(x, bnd.lo[0], bnd.hi[0]);
+        y = norm_coord(y, bnd.lo[1], bnd.hi[1]);
+        z = norm_coord(z, bnd.lo[2], bnd.hi[2]);
         float gp[3] = {0.f, 0.f, 0.f};
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
@@ -810,17 +830,29 @@ __global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet p
             v += __shfl_xor(v, 1, WAVE);            // sum the four pieces of the point
             v += __shfl_xor(v, 2, WAVE);
             v = valid ? v * sc3[k] : 0.0f;
-            if (g == 0) { go_acc[k] += v; gd_acc[k] += v * zz; }
+            if (RENDER) {
+                if (g == 0) { go_acc[k] += v; gd_acc[k] += v * zz; }
+            } else if (g == (s0 >> 4)) {
+                // all four lanes of a point hold its sum: lane (r, g) keeps that of pass g, i.e. of point 16 g + r, and the wave
+                // writes its 64 points once behind the loop.  (With the stores inside the loop, as in the float32 kernel's point
+                // mode, the compiler spilled ~280 registers around them: 1.1 KB of scratch per lane at either bound.)
+                go_acc[k] = v;
+            }
         }
     }
+    if (RENDER) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float a = wave_sum(go_acc[k]);
-        const float b = wave_sum(gd_acc[k]);
-        if (lane == 0) {
-            g_rays_o[ray * 3 + k] = a;
-            g_rays_d[ray * 3 + k] = b;
+        for (int k = 0; k < 3; ++k) {
+            const float a = wave_sum(go_acc[k]);
+            const float b = wave_sum(gd_acc[k]);
+            if (lane == 0) {
+                g_rays_o[unit * 3 + k] = a;
+                g_rays_d[unit * 3 + k] = b;
+            }
         }
+    } else if (16 * g + r < scount) {
+        float* dst = g_rays_o + (base + 16 * g + r) * 3;
+        dst[0] = go_acc[0]; dst[1] = go_acc[1]; dst[2] = go_acc[2];
     }
 }
 
@@ -891,11 +923,8 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     const int lowp = eslam_planes_lowp(planes);
     if (lowp < 0) return 1;
     if (lowp) {
-        if (mode == 0) {
-            eslam_set_error("mixed precision: the backward of free points (eslam_decode_bwd: decoders, planes, point gradients) is not built");
-            return 1;
-        }
-        if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, true); else LAUNCH_MB(1, false, true); }
+        if (mode == 0) { if (g_dec) LAUNCH_MB(0, true, true); else LAUNCH_MB(0, false, true); }      // feat: [N,128] bf16
+        else if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, true); else LAUNCH_MB(1, false, true); }
         else { if (g_dec) LAUNCH_MB(2, true, true); else LAUNCH_MB(2, false, true); }
     }
     else if (mode == 0) { if (g_dec) LAUNCH_MB(0, true, false); else LAUNCH_MB(0, false, false); }
@@ -945,8 +974,11 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     hipLaunchKernelGGL((coord_bwd_kernel<CLv, RD>), grid, block, 0, st, ps, bnd, rays_o, rays_d, z_or_pts, (int)R, \
                        S, g_feat, g_out_a, g_out_b)
         eslam_prof_begin(PROF_COORD_BWD, st);
-        if (lowp)       // (render mode, channels-last half copies: checked above and by eslam_planes_lowp)
-            hipLaunchKernelGGL(coord_bwd_lowp_kernel, grid, block, 0, st, ps, bnd, rays_o, rays_d, z_or_pts, (int)R, S, g_feat,
+        if (lowp && render)       // (channels-last half copies: checked by eslam_planes_lowp)
+            hipLaunchKernelGGL(coord_bwd_lowp_kernel<true>, grid, block, 0, st, ps, bnd, rays_o, rays_d, z_or_pts, (int)R, S, g_feat,
+                               g_out_a, g_out_b);
+        else if (lowp)
+            hipLaunchKernelGGL(coord_bwd_lowp_kernel<false>, grid, block, 0, st, ps, bnd, rays_o, rays_d, z_or_pts, (int)R, S, g_feat,
                                g_out_a, g_out_b);
         else if (cl && render) LAUNCH(true, true);
         else if (cl) LAUNCH(true, false);

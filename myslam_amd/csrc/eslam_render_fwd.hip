@@ -28,6 +28,11 @@ struct LossIn {
 #define FWD_WAVES 2            // waves per SIMD the gather kernels are compiled for: with one plane of loads in flight
                                // ahead of the FMAs the forward kernel needs 195 VGPRs; 2 waves/SIMD measured fastest
 
+// The mixed-precision decode kernels on free points (decode_fwd_kernel<true, ..., true>), none with scratch: SDF only 124
+// VGPRs (list and grid), both fields 126 - 4 waves per SIMD; both fields with saved features 140 - 3 waves.  Asked for 4
+// waves (128 VGPRs) the saving variant spills 40 bytes per lane, so 3 is what is asked and the others take 4 on their own.
+#define DECODE_LP_WAVES 3
+
 // LOWP: the mixed-precision tile of eslam_decode_tile.h (fp16 plane copies, bf16 MFMA decoders); channels-last only.
 template <bool CL, bool SAVE, bool LOSS, bool LOWP>
 __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneSet planes, const eslam_decoders_t dec,
@@ -315,19 +320,23 @@ struct GridPoints {
     }
 };
 
-template <bool CL, bool SDF_ONLY, bool SAVE, typename Src>
-__global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneSet planes, const eslam_decoders_t dec,
+// LOWP: the mixed-precision tile (fp16 plane copies, bf16 MFMA decoders, as render_fwd_kernel's LOWP branches; channels-last
+// only): saved features are the bf16 values the decoders consumed ([N,128] shorts, store_features_lp).
+template <bool CL, bool SDF_ONLY, bool SAVE, typename Src, bool LOWP = false>
+__global__ __launch_bounds__(256, LOWP ? DECODE_LP_WAVES : FWD_WAVES) void decode_fwd_kernel(const PlaneSet planes, const eslam_decoders_t dec,
                                                          const Bound bnd, const Src src,
                                                          float* __restrict__ raw, float* __restrict__ feat_out,
                                                          const int mask_outside) {
+    static_assert(!LOWP || CL, "the half copies are channels-last");
     __shared__ __attribute__((aligned(16))) float wlds[2 * DEC_LDS];
-    stage_decoder_weights(wlds, dec, threadIdx.x, blockDim.x);
+    if (LOWP) stage_decoder_weights_lowp(wlds, dec, threadIdx.x, blockDim.x);
+    else stage_decoder_weights(wlds, dec, threadIdx.x, blockDim.x);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int r = lane & 15, q = lane >> 4;                                  // MFMA role
-    const int gp = gather_point<CL>(lane), gq = gather_piece<CL>(lane);     // gather role
+    const int gp = gather_point<CL>(lane), gq = gather_piece<CL>(lane);     // gather role (LOWP: piece = channels 8gq..8gq+7)
     const int64_t ntiles = src.ntiles();
 
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
@@ -343,7 +352,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneS
         float4_t out[2];
 #pragma unroll
         for (int d = 0; d < (SDF_ONLY ? 1 : 2); ++d) {
-            out[d] = *(const float4_t*)(wlds + d * DEC_LDS + DEC_B3);
+            out[d] = LOWP ? *(const float4_t*)(lp_biases(wlds, d) + 32) : *(const float4_t*)(wlds + d * DEC_LDS + DEC_B3);
 #pragma unroll 1
             for (int b = 0; b < nblk; ++b) {
                 const int oz0 = opaque_zero(b);
@@ -355,6 +364,19 @@ __global__ __launch_bounds__(256, FWD_WAVES) void decode_fwd_kernel(const PlaneS
                 const float py = norm_coord(wy, bnd.lo[1], bnd.hi[1]);
                 const float pz = norm_coord(wz, bnd.lo[2], bnd.hi[2]);
                 float feat[16];
+                if (LOWP) {
+                    gather_features_half(planes, d, px, py, pz, gq, feat, oz0);
+                    if (SAVE) {
+                        if (j < nvalid) store_features_lp(feat_out, pb, d, gq, feat);
+                    }
+                    to_mfma_role<true, 16>(feat, lane);
+                    DecFragLP fl;
+                    load_dec_frag_lp(fl, lp_weights(wlds, d) + oz0, lp_biases(wlds, d) + oz0, r, q);
+                    float4_t a1, a2;
+                    mlp_hidden_lp(fl, feat, a1, a2);
+                    mlp_out_accum_lp(fl, a2, b, r, out[d]);
+                    continue;
+                }
                 gather_features<CL>(planes, d, px, py, pz, gq, feat, oz0);
                 if (SAVE) {
                     if (j < nvalid) store_features(feat_out, pb, d, gq, feat);
@@ -546,8 +568,17 @@ extern "C" int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoder
 #define LAUNCH(CLv, SO, SV) \
     hipLaunchKernelGGL((decode_fwd_kernel<CLv, SO, SV, PointList>), grid, block, 0, st, ps, *dec, bnd, src, raw, feat, \
                        mask_outside)
+#define LAUNCH_LP(SO, SV) \
+    hipLaunchKernelGGL((decode_fwd_kernel<true, SO, SV, PointList, true>), grid, block, 0, st, ps, *dec, bnd, src, raw, feat, \
+                       mask_outside)
+    const int lowp = eslam_planes_lowp(ps.p);       // (the 12 descriptors the kernel reads: sdf_only repeats the geometry planes)
+    if (lowp < 0) return 1;
     eslam_prof_begin(PROF_DECODE_FWD, st);
-    if (sdf_only) {
+    if (lowp) {         // feat: [N,128] bf16
+        if (sdf_only) LAUNCH_LP(true, false);
+        else if (feat) LAUNCH_LP(false, true);
+        else LAUNCH_LP(false, false);
+    } else if (sdf_only) {
         if (cl) LAUNCH(true, true, false);
         else LAUNCH(false, true, false);
     } else if (feat) {
@@ -558,6 +589,7 @@ extern "C" int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoder
         else LAUNCH(false, false, false);
     }
 #undef LAUNCH
+#undef LAUNCH_LP
     eslam_prof_end(PROF_DECODE_FWD, st);
     return eslam_check_launch("decode_fwd_kernel");
 }
@@ -597,7 +629,11 @@ extern "C" int eslam_sdf_grid(const eslam_plane_t* planes, const eslam_decoders_
     dim3 grid((unsigned)(nwg < 8192 ? nwg : 8192)), block(256);
     hipStream_t st = (hipStream_t)stream;
     const int mask_outside = (flags & ESLAM_DECODE_MASK_OUTSIDE) ? 1 : 0;
-    if (cl) hipLaunchKernelGGL((decode_fwd_kernel<true, true, false, GridPoints>), grid, block, 0, st, ps, *dec, bnd, src, vol,
+    const int lowp = eslam_planes_lowp(ps.p);
+    if (lowp < 0) return 1;
+    if (lowp) hipLaunchKernelGGL((decode_fwd_kernel<true, true, false, GridPoints, true>), grid, block, 0, st, ps, *dec, bnd, src,
+                                 vol, nullptr, mask_outside);
+    else if (cl) hipLaunchKernelGGL((decode_fwd_kernel<true, true, false, GridPoints>), grid, block, 0, st, ps, *dec, bnd, src, vol,
                                nullptr, mask_outside);
     else hipLaunchKernelGGL((decode_fwd_kernel<false, true, false, GridPoints>), grid, block, 0, st, ps, *dec, bnd, src, vol,
                             nullptr, mask_outside);

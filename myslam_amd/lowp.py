@@ -10,7 +10,12 @@ Pose gradients: under `ops.mixed_precision(half, ray_grads=True)` rays that requ
 copies too (coord_bwd_lowp_kernel: the bilinear derivative acts on the fp16-rounded texels the forward pass interpolated),
 with the separate losses and with render_batch_ray_with_loss - so the path can track and run the joint mapping iteration
 (slam.SlamConfig.mixed_precision).  Without ray_grads such rays raise, as they always did.
-Still not built: ops.DecodeFn / Decoders.forward on the copies and gradients with respect to free points (eslam_decode_*).
+
+Free points: under `ops.mixed_precision(half, points=True)` ops.DecodeFn (Decoders.forward, get_raw_sdf, get_raw_rgb),
+ops.decode_sdf_only, Mesher.eval_points and ops.sdf_grid - hence Mesher.extract_mesh / get_mesh - run on the copies too, with
+gradients for points, planes and decoders (eslam_decode_bwd; saved features bf16), so the mesh is that of the field that was
+trained and rendered.  Without `points` those calls stay on the float32 masters, bit for bit as outside the context.  The
+depth-less rays' importance sampler stays on the masters either way: sampling is the float32 path.
 
 The copies are the IEEE round-to-nearest-even conversion of the masters, half subnormals included; a master beyond the half
 range (|x| >= 65520) becomes +-inf in its copy and stays inf - nothing clamps it.  A copy is as old as its last refresh: an

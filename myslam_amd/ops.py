@@ -394,6 +394,7 @@ def current_fused_loss():
 
 _half_planes = None
 _half_ray_grads = False
+_half_points = False
 
 
 class mixed_precision:
@@ -403,21 +404,36 @@ class mixed_precision:
     object with `.flat`, the 12 float16 channels_last copies in all_planes order) - refresh it after every optimiser step.
     ray_grads=True: rays that require grad (pose optimisation: tracking, joint mapping) get their gradients from the half
     copies as well (coord_bwd_lowp_kernel) - the derivative of what the forward pass interpolated.  The default refuses such
-    rays, as before this was built: a caller that did not ask keeps its error."""
+    rays, as before this was built: a caller that did not ask keeps its error.
+    points=True: the free-point calls issued inside run on the copies too - DecodeFn (Decoders.forward, get_raw_sdf,
+    get_raw_rgb; saved features bf16, backward with gradients for points, planes and decoders), decode_sdf_only,
+    Mesher.eval_points and sdf_grid, and through them Mesher.extract_mesh / get_mesh: the mesh is that of the field that was
+    trained and rendered.  The default leaves those calls on the float32 masters, bit for bit as outside the context.
+    Planes that are not channels-last raise (the per-call scratch copies of planes_for_kernels have no half counterpart)."""
 
-    def __init__(self, half, ray_grads=False):
+    def __init__(self, half, ray_grads=False, points=False):
         self.half = half
         self.ray_grads = bool(ray_grads)
+        self.points = bool(points)
 
     def __enter__(self):
-        global _half_planes, _half_ray_grads
-        self._prev, _half_planes = (_half_planes, _half_ray_grads), self.half
-        _half_ray_grads = self.ray_grads
+        global _half_planes, _half_ray_grads, _half_points
+        self._prev, _half_planes = (_half_planes, _half_ray_grads, _half_points), self.half
+        _half_ray_grads, _half_points = self.ray_grads, self.points
         return self.half
 
     def __exit__(self, *a):
-        global _half_planes, _half_ray_grads
-        _half_planes, _half_ray_grads = self._prev
+        global _half_planes, _half_ray_grads, _half_points
+        _half_planes, _half_ray_grads, _half_points = self._prev
+
+
+def points_half(geometry_only=False):
+    """The float16 copies a free-point call issued now runs on (the 12 in all_planes order; geometry_only: the six geometry
+    planes twice, as the SDF-only entries take them), or None: outside ops.mixed_precision(half, points=True)."""
+    if _half_planes is None or not _half_points:
+        return None
+    flat = list(_half_planes.flat)
+    return flat[:6] + flat[:6] if geometry_only else flat
 
 
 def join_ray_order(device):
@@ -732,11 +748,14 @@ class DecodeFn(torch.autograd.Function):
         N = pts.shape[0]
         dev = pts.device
         lib = _hip.lib()
-        arr, _ = _hip.make_planes(planes)
+        half = points_half()
+        ctx.half = half
+        arr, _ = _hip.make_planes(planes, half=half)
         dec, keep = _hip.make_decoders(params, dummy_beta)
         needs = any(ctx.needs_input_grad)
         raw = torch.empty(N, 4, device=dev)
-        feat = torch.empty(N, 128, device=dev) if needs else None
+        # saved features: float32, or (mixed precision) the bf16 values the decoders consumed, as in RenderFn
+        feat = torch.empty(N, 128, device=dev, dtype=torch.float32 if half is None else torch.bfloat16) if needs else None
         with _hip.on_device(dev):
             _hip.check(lib.eslam_decode_fwd(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(pts), N, 0,
                                             _hip.ptr(raw), _hip.ptr(feat), _hip.stream_handle(dev)), "eslam_decode_fwd")
@@ -758,9 +777,10 @@ class DecodeFn(torch.autograd.Function):
         grads = None
         if need_planes:
             _, grads = _alloc_plane_grads(planes)
-        arr, _ = _hip.make_planes(planes, grads)
+        arr, _ = _hip.make_planes(planes, grads, half=ctx.half)       # the copies the forward pass read
         dec, keep = _hip.make_decoders(params, dummy_beta)
-        g_dec = torch.empty(_hip.N_DEC_PARAMS, device=dev)
+        # (frozen decoders: NULL, and the kernel skips their gradient work - as RenderFn)
+        g_dec = torch.empty(_hip.N_DEC_PARAMS, device=dev) if any(need[15:27]) else None
         g_pts = torch.empty(N, 3, device=dev) if need[0] else None
         ws = torch.empty(lib.eslam_bwd_workspace_bytes(N), dtype=torch.uint8, device=dev)
         g_raw = _c(g_raw)
@@ -768,7 +788,7 @@ class DecodeFn(torch.autograd.Function):
             _hip.check(lib.eslam_decode_bwd(arr, ctypes.byref(dec), _hip.make_bound(ctx.bound6), _hip.ptr(pts), N,
                                             _hip.ptr(raw), _hip.ptr(feat), _hip.ptr(g_raw), _hip.ptr(g_dec),
                                             _hip.ptr(g_pts), _hip.ptr(ws), _hip.stream_handle(dev)), "eslam_decode_bwd")
-        dec_grads = _split_dec_grads(g_dec)
+        dec_grads = _split_dec_grads(g_dec) if g_dec is not None else [None] * 12
         out = [g_pts, None, None]
         out += [grads[i] if (need_planes and need[3 + i]) else None for i in range(12)]
         out += [dec_grads[i] if need[15 + i] else None for i in range(12)]
@@ -783,7 +803,7 @@ def decode_sdf_only(pts, bound6, all_planes, decoders):
     dev = pts.device
     lib = _hip.lib()
     geo = tuple(all_planes[:3]) + tuple(all_planes[:3])
-    arr, _ = _hip.make_planes(geo)
+    arr, _ = _hip.make_planes(geo, half=points_half(geometry_only=True))
     dec, keep = _hip.make_decoders(decoder_params(decoders), beta_tensor(10, dev))
     out = torch.empty(N, device=dev)
     with _hip.on_device(dev):
@@ -1159,7 +1179,7 @@ def sdf_grid(all_planes, decoders, axes, bound, halfspaces=None):
     if halfspaces is not None and halfspaces.shape[0] > 0:
         hs = _c(halfspaces.detach().to(dev, torch.float32).reshape(-1, 4))
     geo = tuple(all_planes[:3]) + tuple(all_planes[:3])
-    arr, _ = _hip.make_planes(tuple([t.detach() for t in grp] for grp in geo))
+    arr, _ = _hip.make_planes(tuple([t.detach() for t in grp] for grp in geo), half=points_half(geometry_only=True))
     dec, keep = _hip.make_decoders([t.detach() for t in decoder_params(decoders)], beta_tensor(10, dev))
     vol = torch.empty(nx, ny, nz, device=dev)
     with _hip.on_device(dev):

@@ -99,9 +99,9 @@ class HipBackend:
         return lowp.HalfPlanes(all_planes)
 
     def mixed_precision(self, half):
-        """Context manager: render calls inside run on the copies, pose gradients included."""
+        """Context manager: render calls and free-point calls (decoders, mesher) inside run on the copies, pose gradients included."""
         from . import ops
-        return ops.mixed_precision(half, ray_grads=True)
+        return ops.mixed_precision(half, ray_grads=True, points=True)
 
 
 class Slam:

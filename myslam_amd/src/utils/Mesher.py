@@ -35,7 +35,8 @@ def eval_points(self, p, all_planes, decoders):
     dev = p.device
     bound6 = ops.bound_to_host(decoders.bound)
     same_bound = bound6 == ops.bound_to_host(self.bound)
-    arr, _ = _hip.make_planes(tuple([t.detach() for t in grp] for grp in all_planes))
+    # (inside ops.mixed_precision(half, points=True): on the half copies, the field that was trained and rendered)
+    arr, _ = _hip.make_planes(tuple([t.detach() for t in grp] for grp in all_planes), half=ops.points_half())
     dec, keep = _hip.make_decoders([t.detach() for t in ops.decoder_params(decoders)], ops.beta_tensor(10, dev))
     out = torch.empty(N, 4, device=dev)
     lib = _hip.lib()

@@ -1,7 +1,11 @@
 """Per-stage device time of mesh extraction on room0 at the reference's resolution (configs/ESLAM.yaml:14, 0.01 m):
 the frame hull, the field, marching cubes (count + scan, emit), vertex colours and the PLY write.
 
-    python tools/mesh_timing.py [--res 0.01] [--frames 13] [--out DIR] [--level-quantile Q]
+    python tools/mesh_timing.py [--res 0.01] [--frames 13] [--out DIR] [--level-quantile Q] [--mixed]
+
+--mixed: the field (eslam_sdf_grid) and the vertex colours (eval_points) also on the planes' half copies
+(ops.mixed_precision(half, points=True)), against float32 in the same process: the two are timed in alternating windows of
+--mixed-reps calls each, --mixed-rounds times; the JSON gets the median window and the spread of both.
 
 Grid: room0's marching_cubes_bound (configs/Replica/room0.yaml:4).  Planes: scene.synth_planes of room0
 (harness.make_workload(..., planes="synth")), whose field need not cross 0: --level-quantile picks a level that cuts it,
@@ -30,6 +34,9 @@ def main():
     ap.add_argument("--no-ply", action="store_true")
     ap.add_argument("--level", type=float, default=None, help="marching-cubes level (default: the reference's 0)")
     ap.add_argument("--level-quantile", type=float, default=None, help="level = this quantile of the field inside the hull")
+    ap.add_argument("--mixed", action="store_true", help="also time the field and the vertex colours on the half copies")
+    ap.add_argument("--mixed-reps", type=int, default=10)
+    ap.add_argument("--mixed-rounds", type=int, default=5)
     args = ap.parse_args()
     from myslam_amd import harness, ops, scene as scn, synthscene
     from myslam_amd.src.utils import Mesher as M
@@ -82,6 +89,33 @@ def main():
     _, res["marching_cubes_total_ms"] = stage(lambda: ops.marching_cubes(vol, m.level_set, origin, spacing))
     cols, res["colours_ms"] = stage(lambda: M.eval_points(m, verts, wl.planes, wl.decoders)[:, :3])
     print("colours", res["colours_ms"], flush=True)
+    if args.mixed:
+        from myslam_amd import lowp
+        half = lowp.HalfPlanes(wl.planes)
+
+        def on_copies(fn):
+            def g():
+                with ops.mixed_precision(half, points=True):
+                    return fn()
+            return g
+
+        def alternate(f32, mixed):
+            """ms per call (median window, min, max) of both, from alternating windows of device-event time."""
+            t = {"float32": [], "mixed": []}
+            for _ in range(args.mixed_rounds):
+                for name, fn in (("float32", f32), ("mixed", mixed)):
+                    t[name].append(stage(fn, reps=args.mixed_reps)[1])
+            return {k: [sorted(v)[len(v) // 2], min(v), max(v)] for k, v in t.items()}
+
+        field = lambda: ops.sdf_grid(wl.planes, wl.decoders, axes, m.bound, hull.halfspaces)
+        colours = lambda: M.eval_points(m, verts, wl.planes, wl.decoders)[:, :3]
+        field_no_hull = lambda: ops.sdf_grid(wl.planes, wl.decoders, axes, m.bound)
+        res["mixed"] = {"reps": args.mixed_reps, "rounds": args.mixed_rounds, "field_ms": alternate(field, on_copies(field)),
+                        "field_no_hull_ms": alternate(field_no_hull, on_copies(field_no_hull)),
+                        "colours_ms": alternate(colours, on_copies(colours))}
+        d = (on_copies(field)() - field())[vol > -1.0].abs()
+        res["mixed"]["field_abs_diff_max"] = float(d.max())
+        print("mixed", res["mixed"], flush=True)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     if not args.no_ply:
