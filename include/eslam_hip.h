@@ -223,7 +223,10 @@ int eslam_render_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, c
  * the device = d L / d loss (NULL = 1).  loss_out [1] (optional): receives the loss value formed from acc (a ray-sharded
  * caller's acc is only complete after its all-reduce).  g_depth / g_rgb / g_sdf (each optional): FURTHER upstream
  * gradients on the rendered outputs, added to the loss's own.  Everything else as eslam_render_bwd, the ray gradients
- * of the mixed-precision path included.                                                                            */
+ * of the mixed-precision path included.
+ * Both entries: a ray whose upstream gradients are all exactly zero - one that ray_mask, or the mask of eslam_loss_grad,
+ * takes out of the batch - contributes exactly 0.0 to every gradient, and its own g_rays_o / g_rays_d rows are 0.0,
+ * whatever its z_vals hold (the NaN row of a ray whose AABB exit is 0/0 included): zeros are selected, not multiplied. */
 int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                           const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
                           const float* sdf, const float* raw_rgb, const float* feat, const float* depth,
@@ -537,9 +540,12 @@ const char* eslam_profile_name(int kernel_id);
  *   eslam_render_bwd_loss as `acc`.  scratch: 7 x 32 uint32, zeroed once by the caller, left zeroed.
  * eslam_mark_rays: touched [n_blocks] (cleared here) <- 1 for every texel that CAN receive gradient from the batch's rays,
  *   from ray geometry alone: the samples of a ray with depth d lie in [min(0, d - 1.5 tau), max(1.2 d, d + 1.5 tau)], those of
- *   a depth-less ray in [0, AABB exit + 0.01] (Renderer.py:96-100,114-134); the segment is rasterised conservatively into
- *   each plane.  A superset of the texels the ranks' backward passes add to, identical on every rank, known before anything
- *   is sampled.  channels_last planes only (one block = one texel's 32 channels = 128 bytes of the flat gradient buffer);
+ *   a depth-less ray between 0 and far = AABB exit + 0.01 (Renderer.py:96-100,114-134), that is in the ORDERED interval
+ *   [min(0, far), max(0, far)]: far is negative for a ray that starts outside the bound and points away from it.  The
+ *   interval is ordered first and padded (by 1e-5 of its ends + 1e-6) second, its length enters as |hi - lo|, and at least
+ *   one step is taken; the segment is rasterised conservatively into each plane.  A ray whose far is not finite is marked by
+ *   its clamped box in one step.  A superset of the texels the ranks' backward passes add to, identical on every rank,
+ *   known before anything is sampled.  channels_last planes only (one block = one texel's 32 channels = 128 bytes of the flat gradient buffer);
  *   block_base_host[12] = index of each plane's first block in that buffer.
  * eslam_blocks_compact: idx [n_blocks capacity] <- ascending indices of the non-zero bytes of touched; meta[0] <- their
  *   number, meta[1] += 1 (a stamp: the host compares it with its own count of launches before it sizes the all-reduce).

@@ -31,7 +31,9 @@ __device__ __forceinline__ float4_t composite_bwd_chunk(const RayUp up, float be
     const float pex = wave_up1(pin, 1.0f);
     const float T = trans_in * pex;
     const float w = alpha * T;
-    const float gw = up.gd * z + up.gr * cr + up.gg * cg + up.gb * cb;
+    // a ray without a depth gradient (masked out, or depth-less under the mapping loss) contributes a hard zero, not 0 * z: its
+    // z_vals may be anything - the NaN row of a ray whose AABB exit is 0/0 - and 0 * NaN would reach every gradient
+    const float gw = (up.gd != 0.0f ? up.gd * z : 0.0f) + up.gr * cr + up.gg * cg + up.gb * cb;
     const float v = valid ? gw * w : 0.0f;
     // exclusive suffix sum_{k>i} gw_k w_k, formed WITHOUT subtracting v_i from an inclusive sum: w decays
     // geometrically along the ray, so (inclusive - own) would lose the small tail in the rounding of the
@@ -672,6 +674,7 @@ __global__ __launch_bounds__(256, 2) void coord_bwd_kernel(const PlaneSet planes
     const int scount = RENDER ? S : (int)min((int64_t)64, (int64_t)R - base);
     const float sc3[3] = {2.0f / (bnd.hi[0] - bnd.lo[0]), 2.0f / (bnd.hi[1] - bnd.lo[1]), 2.0f / (bnd.hi[2] - bnd.lo[2])};
     float go_acc[3] = {0.f, 0.f, 0.f}, gd_acc[3] = {0.f, 0.f, 0.f};
+    bool live = false;                        // some sample of the ray carries a position gradient that is not exactly zero
 #pragma unroll 1
     for (int s0 = 0; s0 < scount; s0 += 16) {
         const int oz0 = opaque_zero(s0);      // keeps the 12 planes' scalar loads inside this loop (see gather_features)
@@ -715,19 +718,23 @@ __global__ __launch_bounds__(256, 2) void coord_bwd_kernel(const PlaneSet planes
             v = valid ? v * sc3[k] : 0.0f;
             if (RENDER) {
                 if (q == 0) { go_acc[k] += v; gd_acc[k] += v * zz; }
+                live = live || !(v == 0.0f);
             } else if (q == 0 && valid) {
                 g_rays_o[(base + s) * 3 + k] = v;
             }
         }
     }
     if (RENDER) {
+        const bool any_live = __ballot(live) != 0ull;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float a = wave_sum(go_acc[k]);
             const float b = wave_sum(gd_acc[k]);
             if (lane == 0) {
                 g_rays_o[unit * 3 + k] = a;
-                g_rays_d[unit * 3 + k] = b;
+                // a ray none of whose samples carries gradient (masked out by the loss) gets a hard zero, not the sum of 0 * z:
+                // its z_vals may be anything - the NaN row of a ray whose AABB exit is 0/0
+                g_rays_d[unit * 3 + k] = any_live ? b : 0.0f;
             }
         }
     }
@@ -789,6 +796,7 @@ __global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet p
     const int scount = RENDER ? S : (int)min((int64_t)64, (int64_t)R - base);
     const float sc3[3] = {2.0f / (bnd.hi[0] - bnd.lo[0]), 2.0f / (bnd.hi[1] - bnd.lo[1]), 2.0f / (bnd.hi[2] - bnd.lo[2])};
     float go_acc[3] = {0.f, 0.f, 0.f}, gd_acc[3] = {0.f, 0.f, 0.f};
+    bool live = false;                        // some sample of the ray carries a position gradient that is not exactly zero
 #pragma unroll 1
     for (int s0 = 0; s0 < scount; s0 += 16) {
         const int oz0 = opaque_zero(s0);      // keeps the 12 planes' scalar loads inside this loop (see gather_features)
@@ -832,6 +840,7 @@ __global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet p
             v = valid ? v * sc3[k] : 0.0f;
             if (RENDER) {
                 if (g == 0) { go_acc[k] += v; gd_acc[k] += v * zz; }
+                live = live || !(v == 0.0f);
             } else if (g == (s0 >> 4)) {
                 // all four lanes of a point hold its sum: lane (r, g) keeps that of pass g, i.e. of point 16 g + r, and the wave
                 // writes its 64 points once behind the loop.  (With the stores inside the loop, as in the float32 kernel's point
@@ -841,13 +850,16 @@ __global__ __launch_bounds__(256, 3) void coord_bwd_lowp_kernel(const PlaneSet p
         }
     }
     if (RENDER) {
+        const bool any_live = __ballot(live) != 0ull;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float a = wave_sum(go_acc[k]);
             const float b = wave_sum(gd_acc[k]);
             if (lane == 0) {
                 g_rays_o[unit * 3 + k] = a;
-                g_rays_d[unit * 3 + k] = b;
+                // a ray none of whose samples carries gradient (masked out by the loss) gets a hard zero, not the sum of 0 * z:
+                // its z_vals may be anything - the NaN row of a ray whose AABB exit is 0/0
+                g_rays_d[unit * 3 + k] = any_live ? b : 0.0f;
             }
         }
     } else if (16 * g + r < scount) {

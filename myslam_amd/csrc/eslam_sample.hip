@@ -413,7 +413,9 @@ __global__ __launch_bounds__(256, 2) void importance_z_kernel(const PlaneSet pla
     float* out_row = z_vals + (int64_t)ray * S;
     // zu (the jittered stratified samples) is non-decreasing for an ordinary ray: an element's rank is then a bisection in zu
     // plus a scan of the n_imp importance samples.  Checked, not assumed (far <= 0, or a jitter that rounds one ulp past its
-    // bin): any other ray keeps the all-pairs count, which is a permutation whatever the values are.
+    // bin): any other ray keeps the all-pairs count.  Two values that do not compare (a == b, or either is NaN) rank by index,
+    // so the count is a permutation for a row of NaNs too (a ray whose AABB exit is 0/0): the row comes out NaN, as torch.sort
+    // gives it, instead of one element written and the rest of the row left as it was.
     bool inversion = false;
     for (int i = lane; i + 1 < n_strat; i += WAVE) inversion |= !(zu[i] <= zu[i + 1]);
     const bool zu_sorted = __ballot(inversion) == 0ull;
@@ -433,7 +435,7 @@ __global__ __launch_bounds__(256, 2) void importance_z_kernel(const PlaneSet pla
         } else {
             for (int k = 0; k < S; ++k) {
                 const float o2 = (k < n_strat) ? zu[k] : zn[k - n_strat];
-                pos += (o2 < v || (o2 == v && k < i)) ? 1 : 0;
+                pos += (o2 < v || (!(v < o2) && k < i)) ? 1 : 0;
             }
         }
         out_row[pos] = v;

@@ -21,7 +21,10 @@ __device__ __forceinline__ float aabb_exit_plain(const float o[3], const float d
 // One wave per ray.  The samples of a ray lie at parameters z in [t0, t1] of p(z) = o + z d:
 //   depth d > 0 : z_free in [0, 1.2 d], z_surf in [d - 1.5 tau, d + 1.5 tau], jitter stays between the first and last sample
 //                 (Renderer.py:55-61,96-100)                          -> [min(0, d - 1.5 tau), max(1.2 d, d + 1.5 tau)]
-//   depth-less  : uniform samples in [0, far], far = AABB exit + 0.01, importance samples inside their bins (Renderer.py:114-134)
+//   depth-less  : uniform samples between 0 and far = AABB exit + 0.01, importance samples inside their bins
+//                 (Renderer.py:114-134)                               -> [min(0, far), max(0, far)]: a ray that starts outside
+//                 the bound and points away from it has far < 0, and its samples run from far up to 0
+// The interval is ordered BEFORE it is padded, so the pad always widens it.
 // In a plane the texel coordinate is affine in z, x(z) = ax + bx z (normalisation + align_corners scaling), clamped at the
 // border.  The segment is cut into steps of at most one cell along either axis; a step's samples fall into the cells between
 // its end points' cells, whose bilinear corners are the box [i_lo, i_hi + 1] x [j_lo, j_hi + 1] (at most 3 x 3 texels), widened
@@ -59,8 +62,11 @@ __device__ __forceinline__ void mark_rays_block(const MarkArgs& m, int bid, int 
             t0 = fminf(0.0f, gd - c15);
             t1 = fmaxf(1.2f * gd, gd + c15);
         } else {
-            t0 = 0.0f;
-            t1 = aabb_exit_plain(o, d, bnd) + 0.01f;
+            // a NaN far is kept (fminf / fmaxf would drop it and mark the origin's cell): span below is then NaN -> one step,
+            // whose NaN coordinates clamp to texel 0, where the kernels' axis_coord puts such a ray's samples
+            const float far = aabb_exit_plain(o, d, bnd) + 0.01f;
+            t0 = (far != far) ? far : fminf(0.0f, far);
+            t1 = (far != far) ? far : fmaxf(0.0f, far);
         }
         const float pad = 1e-5f * (fabsf(t0) + fabsf(t1)) + 1e-6f;
         t0 -= pad; t1 += pad;
@@ -73,9 +79,9 @@ __device__ __forceinline__ void mark_rays_block(const MarkArgs& m, int bid, int 
             const float su = (float)(pw - 1) / (bnd.hi[au] - bnd.lo[au]), sv = (float)(ph - 1) / (bnd.hi[av] - bnd.lo[av]);
             const float ax = (o[au] - bnd.lo[au]) * su, bx = d[au] * su;
             const float ay = (o[av] - bnd.lo[av]) * sv, by = d[av] * sv;
-            const float span = fmaxf(fabsf(bx), fabsf(by)) * len;
+            const float span = fmaxf(fabsf(bx), fabsf(by)) * fabsf(len);
             // a ray that is not finite (or absurdly long) is marked in one step: its clamped box, at worst the whole plane
-            const int n = (span == span && span < 4096.0f) ? (int)ceilf(span) + 1 : 1;
+            const int n = (span == span && span < 4096.0f) ? max((int)ceilf(span) + 1, 1) : 1;
             const float dt = len / (float)n;
             uint8_t* __restrict__ tp = touched + base.b[pi];
             const float wm1 = (float)(pw - 1), hm1 = (float)(ph - 1);

@@ -88,9 +88,12 @@ def mark_rays(plane_shapes, bound6, rays_o, rays_d, gt_depth, truncation, block_
     hi = torch.tensor(bound6[1::2], dtype=torch.float64)
     c15 = 1.5 * truncation
     has = gd > 0
-    t_all = torch.stack([(lo - o) / d, (hi - o) / d], -1).max(-1).values.min(-1).values + 0.01
-    t0 = torch.where(has, torch.minimum(torch.zeros_like(gd), gd - c15), torch.zeros_like(gd))
-    t1 = torch.where(has, torch.maximum(1.2 * gd, gd + c15), t_all)
+    far = torch.stack([(lo - o) / d, (hi - o) / d], -1).max(-1).values.min(-1).values + 0.01
+    # ordered before it is padded: a depth-less ray that points away from the bound has far < 0, its samples lie in [far, 0]
+    # (torch.minimum / maximum keep a NaN far, as the kernel does)
+    zero = torch.zeros_like(gd)
+    t0 = torch.where(has, torch.minimum(zero, gd - c15), torch.minimum(zero, far))
+    t1 = torch.where(has, torch.maximum(1.2 * gd, gd + c15), torch.maximum(zero, far))
     pad = 1e-5 * (t0.abs() + t1.abs()) + 1e-6
     t0, t1 = t0 - pad, t1 + pad
     eps = 0.02
@@ -100,8 +103,8 @@ def mark_rays(plane_shapes, bound6, rays_o, rays_d, gt_depth, truncation, block_
         su, sv = (w - 1) / (hi[au] - lo[au]), (h - 1) / (hi[av] - lo[av])
         ax, bx = (o[:, au] - lo[au]) * su, d[:, au] * su
         ay, by = (o[:, av] - lo[av]) * sv, d[:, av] * sv
-        span = torch.maximum(bx.abs(), by.abs()) * (t1 - t0)
-        n = torch.where(torch.isfinite(span) & (span < 4096), span.ceil() + 1, torch.ones_like(span)).long()
+        span = torch.maximum(bx.abs(), by.abs()) * (t1 - t0).abs()
+        n = torch.where(torch.isfinite(span) & (span < 4096), span.ceil() + 1, torch.ones_like(span)).long().clamp(min=1)
         nmax = int(n.max())
         k = torch.arange(nmax, dtype=torch.float64)[None]                      # [1, nmax] steps, masked per ray
         dt = ((t1 - t0) / n)[:, None]

@@ -193,14 +193,23 @@ def test_texel_list_and_block_move_kernels():
         assert torch.equal(flat, exp)
 
 
-@pytest.mark.parametrize("scene,zero_frac,state", [("room0", 0.0, "initial"), ("toy", 0.2, "initial"), ("scene0000", 0.1, "trained")])
-def test_rays_marking_contains_every_block_the_backward_touches(scene, zero_frac, state):
+@pytest.mark.parametrize("scene,zero_frac,state,behind", [("room0", 0.0, "initial", 0.0), ("toy", 0.2, "initial", 0.0),
+                                                          ("scene0000", 0.1, "trained", 0.0), ("toy", 1.0, "trained", 0.5)],
+                         ids=["room0-0.0-initial", "toy-0.2-initial", "scene0000-0.1-trained", "toy-1.0-trained-behind"])
+def test_rays_marking_contains_every_block_the_backward_touches(scene, zero_frac, state, behind):
     """eslam_mark_rays (from ray geometry alone, before anything is sampled) must be a superset of the non-zero 128-byte
     blocks of the plane gradients after a backward with fresh random jitter - the ray-sharded exchange relies on it - and
-    equals the tensor-op form the gloo tests run on the CPU."""
+    equals the tensor-op form the gloo tests run on the CPU.
+    behind > 0: the camera stands that far OUTSIDE the bound, behind the face it looks away from (the rays look down -z) -
+    every ray starts outside and, being depth-less (zero_frac 1: no ray with depth marks the same texels on their behalf),
+    has a negative AABB exit: its samples lie in [far, 0]."""
     from myslam_amd import harness, ops, parallel
     dev = _dev()
     wl = harness.make_workload(scene, 3000, 40, 8, device=dev, zero_frac=zero_frac, state=state)
+    if behind:
+        with torch.no_grad():
+            wl.rays_o[:, 2] = float(wl.scene.bound[2, 0]) - behind
+        assert float(ops.aabb_exit(wl.rays_o, wl.rays_d, ops.bound_to_host(wl.scene.bound))[wl.gt_depth == 0].max()) < -0.01
     params = wl.plane_list + ops.decoder_params(wl.decoders) + [wl.decoders.beta]
     fg = parallel.FlatGrads(params)
     n_blocks = sum(p.numel() for p in wl.plane_list) // 32
