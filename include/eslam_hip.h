@@ -280,6 +280,48 @@ int eslam_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float le
                   const double* spacing3_host, const void* workspace, int64_t n_verts, int64_t n_faces, float* verts,
                   int32_t* faces, eslam_stream_t stream);
 
+/* eslam_mc_count for a volume of which only part was observed: weight [nx][ny][nz] float32, a grid point is valid when
+ * its weight > 0.  A cube keeps its faces only when all eight corners are valid; an edge keeps its vertex only when it
+ * crosses the level and at least one of the (up to four) cubes around it is fully valid, so no vertex is left without a
+ * face.  Order, orientation, positions and the workspace are those of eslam_mc_count; eslam_mc_emit follows, unchanged
+ * (it reads the workspace).  With every weight > 0 (and nx, ny, nz >= 2, so that every edge has a cube) the result equals
+ * eslam_mc_count's bit for bit.                                                                                  */
+int eslam_mc_count_masked(const float* vol, const float* weight, int64_t nx, int64_t ny, int64_t nz, float level,
+                          void* workspace, int64_t* counts, eslam_stream_t stream);
+
+/* TSDF fusion of n_frames depth (and colour) images into a dense volume over a box: replaces the integrate step of
+ * open3d's ScalableTSDFVolume in src/utils/Mesher.py:63-128.  tsdf, weight [nx][ny][nz] float32 (z fastest; weight = the
+ * number of observations), color [nx][ny][nz][3] float32 or NULL; voxel (i, j, k) has its centre at
+ * origin + (index + 0.5) voxel.  depths [n_frames][H][W], colors [n_frames][H][W][3] (NULL iff color is NULL),
+ * w2c [n_frames][12] (device): the 3x4 rows (float32) of the float64 inverse, taken on the host, of c2w with its columns 1
+ * and 2 negated (Mesher.py:94-96: the camera looks along +z, x right, y down); depth_max [n_frames] (device): an upper
+ * bound of each frame's depth, used only to skip work (NaN or inf: nothing is skipped).
+ * Per voxel, frames in index order k = 0 .. n_frames - 1, every operation float32, left to right, not contracted:
+ *   p    = origin + (float(i) + 0.5f) * voxel                         (per axis)
+ *   c    = w2c[k] [p, 1]                                              ((r0 px + r1 py) + r2 pz) + t  per row
+ *   skip unless c.z > 0
+ *   u    = (fx c.x) / c.z + cx;   v = (fy c.y) / c.z + cy
+ *   iu   = floor(u + 0.5f);       iv = floor(v + 0.5f)                skip unless 0 <= iu < W and 0 <= iv < H
+ *   d    = depths[k][iv][iu]                                          skip unless d > 0 (NaN skips)
+ *   xn   = (float(iu) - cx) / fx; yn = (float(iv) - cy) / fy
+ *   m    = sqrtf((1 + xn xn) + yn yn)                                 ray length per unit z
+ *   sdf  = (d - c.z) m                                                skip unless sdf > -trunc
+ *   t    = fminf(1, sdf / trunc); W1 = weight + 1
+ *   tsdf = (tsdf weight + t) / W1;  color likewise per channel from colors[k][iv][iu];  weight = W1
+ * The projective running average of open3d's integrate: nearest pixel, distance along the ray.  No weight cap.
+ * Calls compose: frames 0 .. a in one call and a + 1 .. b in the next give the bits of one call with 0 .. b.
+ * A run of 64 voxels along z that no frame of the call updates is neither read nor written.  H, W <= 16384.        */
+int eslam_tsdf_integrate(float* tsdf, float* weight, float* color, int64_t nx, int64_t ny, int64_t nz,
+                         const float* origin3_host, float voxel, float trunc, const float* depths, const float* colors,
+                         const float* w2c, const float* depth_max, int n_frames, int H, int W, float fx, float fy, float cx,
+                         float cy, eslam_stream_t stream);
+
+/* out [n,3] = color [nx][ny][nz][3] sampled trilinearly at pts [n,3] (world coordinates, float32): per axis
+ * g = (p - origin) / voxel - 0.5 (voxel-centre coordinates), i0 = floor(g), t = g - i0, the indices i0 and i0 + 1 clamped
+ * to the volume.  On a marching-cubes vertex of the volume this is the linear blend of the edge's two voxels.      */
+int eslam_tsdf_sample_color(const float* color, int64_t nx, int64_t ny, int64_t nz, const float* origin3_host, float voxel,
+                            const float* pts, int64_t n, float* out, eslam_stream_t stream);
+
 /* Mesh culling: the visibility test of src/tools/cull_mesh.py:61-104 for a chunk of n_frames frames in one launch.
  * For every vertex p of verts [n_verts,3] whose seen[p] is 0 and every frame k, with w2c[k] the 3x4 rows (float32,
  * inverted from c2w on the host in float64) of w2c [n_frames][12] (device):

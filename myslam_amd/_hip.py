@@ -101,6 +101,10 @@ SIGNATURES = {
     "eslam_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "eslam_mc_count": (_i, [_vp, _i64, _i64, _i64, _f, _vp, _vp, _vp]),
     "eslam_mc_emit": (_i, [_vp, _i64, _i64, _i64, _f, ctypes.POINTER(_d), ctypes.POINTER(_d), _vp, _i64, _i64, _vp, _vp, _vp]),
+    "eslam_mc_count_masked": (_i, [_vp, _vp, _i64, _i64, _i64, _f, _vp, _vp, _vp]),
+    "eslam_tsdf_integrate": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_f), _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i,
+                                  _f, _f, _f, _f, _vp]),
+    "eslam_tsdf_sample_color": (_i, [_vp, _i64, _i64, _i64, ctypes.POINTER(_f), _f, _vp, _i64, _vp, _vp]),
     "eslam_cull_vertices": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _i, _i, _f, _i, _vp, _vp]),
     "eslam_nn_grid_plan": (_i, [_i64, _BP, _GP]),
     "eslam_nn_workspace_bytes": (_i64, [_GP, _i64]),

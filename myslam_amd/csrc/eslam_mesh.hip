@@ -45,7 +45,20 @@ __device__ __forceinline__ int mc_edge_vertex(const McGrid& g, int64_t i, int e,
     return vbase[owner] + __popc((unsigned)ebits[owner] & ((1u << axis) - 1u));
 }
 
-__global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float* __restrict__ vol, const McGrid g, const float level,
+// masked mode: the cube with lower corner (ix, iy, iz) exists and all eight of its corners were observed (weight > 0)
+__device__ __forceinline__ bool mc_cube_valid(const float* __restrict__ weight, const McGrid& g, int64_t ix, int64_t iy,
+                                              int64_t iz) {
+    if (ix < 0 || iy < 0 || iz < 0 || ix + 1 >= g.nx || iy + 1 >= g.ny || iz + 1 >= g.nz) return false;
+    const float* w = weight + (ix * g.ny + iy) * g.nz + iz;
+    return w[0] > 0.0f && w[1] > 0.0f && w[g.nz] > 0.0f && w[g.nz + 1] > 0.0f && w[g.sx] > 0.0f && w[g.sx + 1] > 0.0f &&
+           w[g.sx + g.nz] > 0.0f && w[g.sx + g.nz + 1] > 0.0f;
+}
+
+// MASKED (eslam_mc_count_masked): a cube keeps its case only when it is valid, an edge its crossing bit only when one of
+// the (up to four) cubes around it is; the emit kernels read nothing but these bytes, so they serve both modes
+template <bool MASKED>
+__global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float* __restrict__ vol, const float* __restrict__ weight,
+                                                              const McGrid g, const float level,
                                                               uint8_t* __restrict__ ebits, uint8_t* __restrict__ cases,
                                                               int64_t* __restrict__ chunk_counts) {
     __shared__ int lds[MC_THREADS / 64];
@@ -61,9 +74,21 @@ __global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float* __res
         const bool bx = hx ? vol[i + g.sx] < level : b0;
         const bool by = hy ? vol[i + g.nz] < level : b0;
         const bool bz = hz ? vol[i + 1] < level : b0;
-        const int e = (int)(bx != b0) | ((int)(by != b0) << 1) | ((int)(bz != b0) << 2);
+        int e = (int)(bx != b0) | ((int)(by != b0) << 1) | ((int)(bz != b0) << 2);
         int cube = 0;
-        if (hx && hy && hz) {
+        if (MASKED && e) {
+            // the cubes around the edge along axis a: lower corners at the point minus 0 or 1 along the two other axes
+            const bool v00 = mc_cube_valid(weight, g, ix, iy, iz);
+            int keep = 0;
+            if (e & 1) keep |= (int)(v00 || mc_cube_valid(weight, g, ix, iy - 1, iz) || mc_cube_valid(weight, g, ix, iy, iz - 1) ||
+                                     mc_cube_valid(weight, g, ix, iy - 1, iz - 1));
+            if (e & 2) keep |= (int)(v00 || mc_cube_valid(weight, g, ix - 1, iy, iz) || mc_cube_valid(weight, g, ix, iy, iz - 1) ||
+                                     mc_cube_valid(weight, g, ix - 1, iy, iz - 1)) << 1;
+            if (e & 4) keep |= (int)(v00 || mc_cube_valid(weight, g, ix - 1, iy, iz) || mc_cube_valid(weight, g, ix, iy - 1, iz) ||
+                                     mc_cube_valid(weight, g, ix - 1, iy - 1, iz)) << 2;
+            e = keep;
+        }
+        if (hx && hy && hz && (!MASKED || mc_cube_valid(weight, g, ix, iy, iz))) {
             const bool bxy = vol[i + g.sx + g.nz] < level, bxz = vol[i + g.sx + 1] < level;
             const bool byz = vol[i + g.nz + 1] < level, bxyz = vol[i + g.sx + g.nz + 1] < level;
             cube = (int)b0 | ((int)bx << 1) | ((int)by << 2) | ((int)bxy << 3) | ((int)bz << 4) | ((int)bxz << 5) |
@@ -215,22 +240,33 @@ static McWork mc_work(void* ws, int64_t N) {
     return w;
 }
 
-extern "C" int eslam_mc_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
-                              int64_t* counts, eslam_stream_t stream) {
+template <bool MASKED>
+static int mc_count(const char* who, const float* vol, const float* weight, int64_t nx, int64_t ny, int64_t nz, float level,
+                    void* workspace, int64_t* counts, eslam_stream_t stream) {
     McGrid g;
-    if (!mc_grid("eslam_mc_count", nx, ny, nz, g)) return 1;
-    if (!vol || !workspace || !counts) {
-        eslam_set_error("eslam_mc_count: null argument");
+    if (!mc_grid(who, nx, ny, nz, g)) return 1;
+    if (!vol || !workspace || !counts || (MASKED && !weight)) {
+        eslam_set_error("%s: null argument", who);
         return 1;
     }
     const McWork w = mc_work(workspace, g.N);
     const int64_t nch = mc_chunks(g.N);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nch), dim3(MC_THREADS), 0, st, vol, g, level, w.ebits, w.cases,
-                       w.chunk_counts);
+    hipLaunchKernelGGL(mc_count_kernel<MASKED>, dim3((unsigned)nch), dim3(MC_THREADS), 0, st, vol, weight, g, level, w.ebits,
+                       w.cases, w.chunk_counts);
     if (eslam_check_launch("mc_count_kernel")) return 1;
     hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.chunk_counts, nch, counts);
     return eslam_check_launch("mc_scan_kernel");
+}
+
+extern "C" int eslam_mc_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
+                              int64_t* counts, eslam_stream_t stream) {
+    return mc_count<false>("eslam_mc_count", vol, nullptr, nx, ny, nz, level, workspace, counts, stream);
+}
+
+extern "C" int eslam_mc_count_masked(const float* vol, const float* weight, int64_t nx, int64_t ny, int64_t nz, float level,
+                                     void* workspace, int64_t* counts, eslam_stream_t stream) {
+    return mc_count<true>("eslam_mc_count_masked", vol, weight, nx, ny, nz, level, workspace, counts, stream);
 }
 
 extern "C" int eslam_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float level, const double* origin3_host,

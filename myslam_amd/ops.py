@@ -4,6 +4,7 @@ autograd graph the reference's Mapper/Tracker call .backward() on); all arithmet
 Nothing in this file computes on the CPU: tensors that are not on a GPU raise.
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -1232,6 +1233,133 @@ def marching_cubes(vol, level, origin, spacing):
     ws, counts = mc_count(vol, level)
     n_verts, n_faces = (int(v) for v in counts.tolist())
     return mc_emit(vol, level, origin, spacing, ws, n_verts, n_faces)
+
+
+def mc_count_masked(vol, weight, level):
+    """mc_count for a partly observed volume (eslam_mc_count_masked): grid points with weight > 0 are valid, a cube emits
+    faces only when its eight corners are, an edge its vertex only when a fully valid cube touches it."""
+    _hip.require_gpu_f32("vol", vol)
+    _hip.require_gpu_f32("weight", weight)
+    if vol.dim() != 3 or not vol.is_contiguous() or weight.shape != vol.shape or not weight.is_contiguous() or \
+            weight.device != vol.device:
+        raise RuntimeError(f"marching_cubes: vol and weight must be contiguous [nx,ny,nz] tensors of one shape on one device, "
+                           f"got {tuple(vol.shape)} and {tuple(weight.shape)}")
+    dev = vol.device
+    ws = torch.empty(mc_workspace_bytes(vol.shape), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_mc_count_masked(_hip.ptr(vol), _hip.ptr(weight), *vol.shape, float(level), _hip.ptr(ws),
+                                                    _hip.ptr(counts), _hip.stream_handle(dev)), "eslam_mc_count_masked")
+    return ws, counts
+
+
+def marching_cubes_masked(vol, weight, level, origin, spacing):
+    """marching_cubes over the observed part of a volume (weight > 0): same vertex and face order; with every weight
+    positive the result is marching_cubes' bit for bit."""
+    ws, counts = mc_count_masked(vol, weight, level)
+    n_verts, n_faces = (int(v) for v in counts.tolist())
+    return mc_emit(vol, level, origin, spacing, ws, n_verts, n_faces)
+
+
+# ----------------------------------------------------------------------------------------------
+# TSDF fusion of RGB-D frames (reference src/utils/Mesher.py:63-128, open3d's ScalableTSDFVolume): DESIGN.md section 17
+# ----------------------------------------------------------------------------------------------
+class TSDFVolume:
+    """A dense TSDF volume over the box `bound` ([3,2]): dims = ceil((hi - lo) / voxel) voxels per axis, voxel (i, j, k)
+    centred at origin + (index + 0.5) voxel, origin = lo.  tsdf and weight [nx,ny,nz] float32 (weight = the number of
+    observations), color [nx,ny,nz,3] float32 or None, all zero at first, on the GPU (eslam_tsdf_integrate has no CPU
+    fallback).  Raises RuntimeError, with the byte count, when the device has less memory free than the arrays need."""
+
+    def __init__(self, bound, voxel, trunc, color=True, device=None):
+        b = torch.as_tensor(bound).detach().to("cpu", torch.float64).reshape(3, 2)
+        self.voxel = float(torch.tensor(float(voxel), dtype=torch.float32))        # what the kernel sees
+        self.trunc = float(torch.tensor(float(trunc), dtype=torch.float32))
+        if not (self.voxel > 0 and self.trunc > 0):
+            raise RuntimeError(f"TSDFVolume: voxel {voxel} and trunc {trunc} must be positive")
+        self.dims = tuple(int(math.ceil(float(b[k, 1] - b[k, 0]) / float(voxel))) for k in range(3))
+        if min(self.dims) < 1:
+            raise RuntimeError(f"TSDFVolume: empty bound {b.tolist()}")
+        self.origin = tuple(float(v) for v in b[:, 0].to(torch.float32))
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"TSDFVolume: expected a GPU device (got {dev}); TSDF fusion has no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        n = self.dims[0] * self.dims[1] * self.dims[2]
+        need = 4 * n * (5 if color else 2)
+        free, _ = torch.cuda.mem_get_info(dev)
+        if free < need:
+            raise RuntimeError(f"TSDFVolume: {self.dims[0]} x {self.dims[1]} x {self.dims[2]} voxels need {need} bytes, "
+                               f"{free} bytes are free on {dev}")
+        self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=dev)
+        self.weight = torch.zeros(self.dims, dtype=torch.float32, device=dev)
+        self.color = torch.zeros(self.dims + (3,), dtype=torch.float32, device=dev) if color else None
+
+    def _flush(self, depths, colors, c2ws, K):
+        dev = self.device
+        fx, fy, cx, cy = (float(k) for k in K)
+        d = _c(torch.stack([torch.as_tensor(x).detach().to(dev, torch.float32) for x in depths]))
+        if d.dim() != 3:
+            raise RuntimeError(f"TSDFVolume.integrate: depth images must be [H,W], got {tuple(d.shape[1:])}")
+        n, H, W = (int(v) for v in d.shape)
+        col = None
+        if self.color is not None:
+            col = _c(torch.stack([torch.as_tensor(x).detach().to(dev, torch.float32) for x in colors]))
+            if tuple(col.shape) != (n, H, W, 3):
+                raise RuntimeError(f"TSDFVolume.integrate: colour images must be [H,W,3] like the depth, got {tuple(col.shape[1:])}")
+        w2c = _w2c_rows(torch.stack([torch.as_tensor(c).detach().to("cpu", torch.float64).reshape(4, 4) for c in c2ws]), dev,
+                        flip_yz=True)
+        depth_max = _c(d.reshape(n, -1).amax(dim=1))
+        o3 = (ctypes.c_float * 3)(*self.origin)
+        with _hip.on_device(dev):
+            _hip.check(_hip.lib().eslam_tsdf_integrate(_hip.ptr(self.tsdf), _hip.ptr(self.weight), _hip.ptr(self.color),
+                                                       *self.dims, o3, self.voxel, self.trunc, _hip.ptr(d), _hip.ptr(col),
+                                                       _hip.ptr(w2c), _hip.ptr(depth_max), n, H, W, fx, fy, cx, cy,
+                                                       _hip.stream_handle(dev)), "eslam_tsdf_integrate")
+
+    def integrate(self, frames, K, chunk=32):
+        """Fuse `frames`, an iterable of (idx, colour [H,W,3], depth [H,W], c2w [4,4]) as the dataset readers and
+        synthscene.make_sequence yield them (any device; colour is not read when the volume has none), K = (fx, fy, cx, cy).
+        Poses are the reference's (camera looks along -z, y up): columns 1 and 2 are negated here, as Mesher.py:94-96 does.
+        Frames are streamed `chunk` at a time, one launch each, applied in the order given; each chunk's poses are inverted
+        on the host in float64, its depth maxima are taken on the device (no per-frame sync).  The result does not depend
+        on `chunk`."""
+        chunk = max(1, int(chunk))
+        depths, colors, c2ws = [], [], []
+        for _, colour, depth, c2w in frames:
+            depths.append(depth)
+            colors.append(colour)
+            c2ws.append(c2w)
+            if len(c2ws) == chunk:
+                self._flush(depths, colors, c2ws, K)
+                depths, colors, c2ws = [], [], []
+        if c2ws:
+            self._flush(depths, colors, c2ws, K)
+        return self
+
+    def extract_mesh(self, level=0.0):
+        """(verts float32 [V,3], faces int32 [F,3], colours float32 [V,3] or None) on the device: marching cubes over the
+        observed voxels (marching_cubes_masked), vertices at origin + (i + 0.5 + t) voxel, colours sampled trilinearly from
+        the colour volume (on an edge vertex: the blend of the edge's two voxels)."""
+        origin = tuple(o + 0.5 * self.voxel for o in self.origin)
+        verts, faces = marching_cubes_masked(self.tsdf, self.weight, level, origin, (self.voxel,) * 3)
+        if self.color is None:
+            return verts, faces, None
+        return verts, faces, self.sample_color(verts)
+
+    def sample_color(self, pts):
+        """float32 [N,3]: the colour volume sampled trilinearly at the world points pts [N,3] (eslam_tsdf_sample_color)."""
+        if self.color is None:
+            raise RuntimeError("TSDFVolume.sample_color: the volume has no colour")
+        p = _gpu_points("pts", pts, self.device)
+        out = torch.empty(p.shape[0], 3, dtype=torch.float32, device=self.device)
+        o3 = (ctypes.c_float * 3)(*self.origin)
+        with _hip.on_device(self.device):
+            _hip.check(_hip.lib().eslam_tsdf_sample_color(_hip.ptr(self.color), *self.dims, o3, self.voxel, _hip.ptr(p),
+                                                          p.shape[0], _hip.ptr(out), _hip.stream_handle(self.device)),
+                       "eslam_tsdf_sample_color")
+        return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -7,6 +7,10 @@ Functions with the reference's signatures, to be bound onto its Mesher class one
     Mesher.get_bound_from_frames = hip_mesher.get_bound_from_frames    # Mesher.py:63-128
     Mesher.get_mesh = hip_mesher.get_mesh                              # Mesher.py:188-262
 
+and, for the reference's own hull construction (a TSDF fusion of the keyframes, ops.TSDFVolume) instead of the default:
+
+    Mesher.get_bound_from_frames = hip_mesher.get_bound_from_frames_tsdf
+
 eval_points: same arguments, same [N,4] result (rgb, sdf with -1 outside the bound).  The bound test is folded into the
 decode kernel (ESLAM_DECODE_MASK_OUTSIDE), so a batch is one launch instead of a decode plus 8 mask / index ops, and all
 batches write into one output tensor (no torch.cat).
@@ -140,6 +144,21 @@ def get_bound_from_frames(self, keyframe_dict, scale=1):
     """Mesher.py:63-128 without open3d: a FrameHull around the keyframes' back-projected depth and camera centres.
     (`scale` only set the reference's TSDF voxel size.)"""
     return FrameHull(halfspaces_from_points(keyframe_points(self, keyframe_dict), self.mesh_bound_scale))
+
+
+def get_bound_from_frames_tsdf(self, keyframe_dict, scale=1, voxel=None):
+    """Mesher.py:63-128 by the reference's own construction, to be bound in place of get_bound_from_frames by whoever wants
+    it: the keyframes' depth fused with est_c2w into a TSDF volume over marching_cubes_bound (ops.TSDFVolume: voxel
+    4 scale / 512 unless given, truncation 0.04 scale, no colour), its mesh's vertices plus the camera centres bounded by
+    the FrameHull's support half-spaces and scaled by mesh_bound_scale.  Deviations from open3d: DESIGN.md section 17."""
+    voxel = 4.0 * scale / 512.0 if voxel is None else voxel
+    dev = keyframe_dict[0]["depth"].device
+    vol = ops.TSDFVolume(self.marching_cubes_bound, voxel, 0.04 * scale, color=False, device=dev)
+    K = (float(self.fx), float(self.fy), float(self.cx), float(self.cy))
+    vol.integrate(((i, None, kf["depth"], kf["est_c2w"]) for i, kf in enumerate(keyframe_dict)), K)
+    verts, _, _ = vol.extract_mesh()
+    cams = torch.stack([kf["est_c2w"][:3, 3].to(verts.device, torch.float32) for kf in keyframe_dict])
+    return FrameHull(halfspaces_from_points(torch.cat([verts, cams], 0), self.mesh_bound_scale))
 
 
 # ----------------------------------------------------------------------------------------------
