@@ -322,6 +322,33 @@ int eslam_tsdf_integrate(float* tsdf, float* weight, float* color, int64_t nx, i
 int eslam_tsdf_sample_color(const float* color, int64_t nx, int64_t ny, int64_t nz, const float* origin3_host, float voxel,
                             const float* pts, int64_t n, float* out, eslam_stream_t stream);
 
+/* Frame preparation: the decoded images of one RGB-D frame -> the float32 images the loop samples; replaces the host
+ * arithmetic of src/utils/datasets.py:88-114 (BaseDataset.__getitem__).  rgb [Hc][Wc][3] uint8 (RGB), depth [Hd][Wd] uint16,
+ * both on the device.  Stages, each absent when it is the identity:
+ *   1  colour resized to (Hd, Wd): bilinear on pixel centres (cv2.resize; F.interpolate align_corners=False)
+ *   2  both resized to crop_size (crop_h, crop_w; 0, 0 = none): colour bilinear with aligned corners, depth nearest with
+ *      torch's float32 rule  src = min(int(floorf(dst * (float(in) / float(out)))), in - 1)
+ *   3  crop_edge pixels dropped on every side
+ *   4  colour / 255;  depth = (float(raw) / png_depth_scale) * scale, two float32 operations, the division a true one
+ * color_out [H'][W'][3], depth_out [H'][W'] float32 with (H', W') = eslam_frame_out_shape(...).  The colour stages are
+ * evaluated per output pixel by nested taps (no intermediate image); tap positions and weights follow torch's upsample
+ * arithmetic in float64 (src = in/out (dst + 0.5) - 0.5 clamped at 0, or (in-1)/(out-1) dst with aligned corners;
+ * i0 = int(src), i1 = i0 + (i0 < in - 1), w1 = src - i0, w0 = 1 - w1), are rounded to float32, and the blends
+ * wy0 (wx0 a + wx1 b) + wy1 (wx0 c + wx1 d) are float32 on byte values, the division by 255 last.  With no stage at all
+ * (and 16-byte aligned outputs) one flat launch converts both images four elements per lane.  Sizes <= 16384.        */
+int eslam_frame_out_shape(int Hc, int Wc, int Hd, int Wd, int crop_h, int crop_w, int crop_edge, int* H_out_host,
+                          int* W_out_host);
+int eslam_frame_prepare(const uint8_t* rgb, int Hc, int Wc, const uint16_t* depth, int Hd, int Wd, int crop_h, int crop_w,
+                        int crop_edge, float png_depth_scale, float scale, float* color_out, float* depth_out,
+                        eslam_stream_t stream);
+
+/* Lens undistortion of a byte image (TUM RGB-D; cv2.undistort restated as F.grid_sample(bilinear, zeros,
+ * align_corners=True) in datasets.undistort): out [H][W][3] uint8 = rgb sampled at grid [H][W][2] (float32, x then y in
+ * [-1, 1] coordinates; datasets.undistort_map), float32 in the order of torch's CPU kernel: pixel = (g + 1) ((size - 1) / 2),
+ * fractions w, n and e = 1 - w, s = 1 - n, value = fma(se, w n, fma(sw, e n, fma(ne, w s, nw (e s)))) with taps outside
+ * the image 0, then round-half-even and clamp to [0, 255].  out must not be rgb.                                      */
+int eslam_frame_undistort(const uint8_t* rgb, const float* grid, int H, int W, uint8_t* out, eslam_stream_t stream);
+
 /* Mesh culling: the visibility test of src/tools/cull_mesh.py:61-104 for a chunk of n_frames frames in one launch.
  * For every vertex p of verts [n_verts,3] whose seen[p] is 0 and every frame k, with w2c[k] the 3x4 rows (float32,
  * inverted from c2w on the host in float64) of w2c [n_frames][12] (device):

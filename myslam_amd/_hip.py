@@ -105,6 +105,9 @@ SIGNATURES = {
     "eslam_tsdf_integrate": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.POINTER(_f), _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i,
                                   _f, _f, _f, _f, _vp]),
     "eslam_tsdf_sample_color": (_i, [_vp, _i64, _i64, _i64, ctypes.POINTER(_f), _f, _vp, _i64, _vp, _vp]),
+    "eslam_frame_out_shape": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "eslam_frame_prepare": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
+    "eslam_frame_undistort": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "eslam_cull_vertices": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _f, _f, _f, _f, _i, _i, _f, _i, _vp, _vp]),
     "eslam_nn_grid_plan": (_i, [_i64, _BP, _GP]),
     "eslam_nn_workspace_bytes": (_i64, [_GP, _i64]),

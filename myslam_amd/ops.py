@@ -1363,6 +1363,56 @@ class TSDFVolume:
 
 
 # ----------------------------------------------------------------------------------------------
+# frame preparation (src/utils/datasets.py: BaseDataset.__getitem__ on the device)
+# ----------------------------------------------------------------------------------------------
+def frame_out_shape(color_hw, depth_hw, crop_size, crop_edge):
+    """(H', W') of prepare_frame's outputs (eslam_frame_out_shape; host arithmetic, needs no GPU)."""
+    ch, cw = (0, 0) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+    H, W = ctypes.c_int(0), ctypes.c_int(0)
+    _hip.check(_hip.lib().eslam_frame_out_shape(int(color_hw[0]), int(color_hw[1]), int(depth_hw[0]), int(depth_hw[1]), ch, cw,
+                                                int(crop_edge), ctypes.byref(H), ctypes.byref(W)), "eslam_frame_out_shape")
+    return H.value, W.value
+
+
+def prepare_frame(rgb_u8, depth_u16, spec):
+    """(colour [H',W',3] float32, depth [H',W'] float32) on the device from the decoded images of one frame: rgb_u8
+    [Hc,Wc,3] uint8 and depth_u16 [Hd,Wd] uint16 (or the same bits as int16), both on the GPU and contiguous.  `spec` is
+    the dataset's datasets.FrameSpec.  What BaseDataset.__getitem__ returns, computed by eslam_frame_undistort (only with
+    a distortion map) and eslam_frame_prepare on the caller's current stream; no synchronisation."""
+    dev = rgb_u8.device
+    if not rgb_u8.is_cuda or depth_u16.device != dev:
+        raise RuntimeError(f"prepare_frame: expected both images on one GPU (got {rgb_u8.device}, {depth_u16.device}); "
+                           "frame preparation has no CPU fallback")
+    if rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or not rgb_u8.is_contiguous():
+        raise RuntimeError(f"prepare_frame: rgb must be a contiguous [H,W,3] uint8 tensor, got {rgb_u8.dtype} {tuple(rgb_u8.shape)}")
+    if depth_u16.dtype not in (torch.uint16, torch.int16) or depth_u16.dim() != 2 or not depth_u16.is_contiguous():
+        raise RuntimeError(f"prepare_frame: depth must be a contiguous [H,W] uint16 tensor, got {depth_u16.dtype} "
+                           f"{tuple(depth_u16.shape)}")
+    Hc, Wc = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
+    Hd, Wd = int(depth_u16.shape[0]), int(depth_u16.shape[1])
+    ch, cw = (0, 0) if spec.crop_size is None else spec.crop_size
+    Ho, Wo = frame_out_shape((Hc, Wc), (Hd, Wd), spec.crop_size, spec.crop_edge)
+    lib = _hip.lib()
+    color = torch.empty(Ho, Wo, 3, dtype=torch.float32, device=dev)
+    depth = torch.empty(Ho, Wo, dtype=torch.float32, device=dev)
+    with _hip.on_device(dev):
+        st = _hip.stream_handle(dev)
+        grid = spec.grid_on(dev)
+        if grid is not None:
+            if tuple(grid.shape) != (Hc, Wc, 2) or grid.dtype != torch.float32 or not grid.is_contiguous():
+                raise RuntimeError(f"prepare_frame: the undistortion map is {tuple(grid.shape)} {grid.dtype}, the colour image "
+                                   f"{Hc} x {Wc}")
+            flat = torch.empty_like(rgb_u8)
+            _hip.check(lib.eslam_frame_undistort(_hip.ptr(rgb_u8), _hip.ptr(grid), Hc, Wc, _hip.ptr(flat), st),
+                       "eslam_frame_undistort")
+            rgb_u8 = flat
+        _hip.check(lib.eslam_frame_prepare(_hip.ptr(rgb_u8), Hc, Wc, _hip.ptr(depth_u16), Hd, Wd, ch, cw, spec.crop_edge,
+                                           spec.png_depth_scale, spec.scale, _hip.ptr(color), _hip.ptr(depth), st),
+                   "eslam_frame_prepare")
+    return color, depth
+
+
+# ----------------------------------------------------------------------------------------------
 # reconstruction evaluation (reference src/tools/cull_mesh.py, src/tools/eval_recon.py): culling, nearest neighbours,
 # ICP moments, surface sampling
 # ----------------------------------------------------------------------------------------------

@@ -1,0 +1,46 @@
+"""Run the system on a dataset from its YAML config, as the reference's run.py does:
+
+    python -m myslam_amd.run configs/Replica/room0.yaml [--input_folder D] [--output D] [--graph]
+
+The config is read over the file its `inherit_from` names and over the defaults file: configs/ESLAM.yaml from the
+working directory, as the reference has it, else the nearest ESLAM.yaml in a directory above the config.  --graph replays
+every optimisation iteration as a captured hipGraph (slam_graph.GraphedSlam)."""
+import argparse
+import os
+
+from .src import config
+from .src.ESLAM import ESLAM
+
+
+def default_config_for(path):
+    """configs/ESLAM.yaml as the reference names it, else the nearest ESLAM.yaml in a directory above `path`."""
+    if os.path.exists('configs/ESLAM.yaml'):
+        return 'configs/ESLAM.yaml'
+    d = os.path.dirname(os.path.abspath(path))
+    while True:
+        cand = os.path.join(d, 'ESLAM.yaml')
+        if os.path.exists(cand):
+            return cand
+        up = os.path.dirname(d)
+        if up == d:
+            raise FileNotFoundError(f"no defaults file: configs/ESLAM.yaml does not exist here and no ESLAM.yaml lies above {path}")
+        d = up
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='Arguments for running ESLAM.')
+    parser.add_argument('config', type=str, help='Path to config file.')
+    parser.add_argument('--input_folder', type=str,
+                        help='input folder, this have higher priority, can overwrite the one in config file')
+    parser.add_argument('--output', type=str,
+                        help='output folder, this have higher priority, can overwrite the one in config file')
+    parser.add_argument('--graph', action='store_true', help='replay the iterations as captured hipGraphs')
+    args = parser.parse_args(argv)
+    cfg = config.load_config(args.config, default_config_for(args.config))
+    eslam = ESLAM(cfg, args)
+    eslam.run()
+    return eslam
+
+
+if __name__ == '__main__':
+    main()

@@ -18,6 +18,7 @@ Planes are allocated with torch.channels_last strides: same logical [1, C, h, w]
 uses (so callers index them identically), but one texel's C=32 channels are 128 contiguous bytes, which
 is what the HIP gather/scatter kernels coalesce on.  NCHW-contiguous planes are accepted too (slower).
 """
+import os
 from dataclasses import dataclass, field
 from typing import List, Tuple
 
@@ -147,6 +148,20 @@ def make_scene(name):
     return Scene(name=name, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, bound=bound,
                  plane_shapes=plane_shapes(bound), n_stratified=s["n_stratified"],
                  n_importance=s["n_importance"], learnable_beta=s["learnable_beta"])
+
+
+def scene_from_config(cfg, name=None):
+    """The Scene of a loaded config dict (src/config.load_config): what ESLAM.__init__ derives from it at start-up
+    (update_cam, load_bound, init_planes' shapes; reference src/ESLAM.py:68-78) plus the sample counts of `rendering`."""
+    H, W, fx, fy, cx, cy = update_cam(cfg["cam"])
+    bound = load_bound(cfg["mapping"]["bound"], cfg["scale"], cfg["planes_res"]["bound_dividable"])
+    r = cfg["rendering"]
+    if name is None:
+        name = os.path.basename(os.path.normpath(cfg.get("data", {}).get("input_folder", ""))) or cfg.get("dataset", "scene")
+    return Scene(name=name, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, bound=bound,
+                 plane_shapes=plane_shapes(bound, cfg["model"]["c_dim"], cfg["planes_res"], cfg["c_planes_res"]),
+                 n_stratified=r["n_stratified"], n_importance=r["n_importance"], learnable_beta=r["learnable_beta"],
+                 truncation=cfg["model"]["truncation"], scale=cfg["scale"])
 
 
 def new_plane(shape, device="cpu", dtype=torch.float32):

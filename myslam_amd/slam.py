@@ -55,6 +55,25 @@ class SlamConfig:
     # decoders (lowp.py); the float32 planes stay the optimiser's masters.  Needs a backend with the two hooks below.
     mixed_precision: bool = False
 
+    @classmethod
+    def from_config(cls, cfg):
+        """The `tracking` and `mapping` sections of a loaded config dict (src/config.load_config), plus an optional
+        top-level `mixed_precision` key of this project's own (default False).  The class defaults are what
+        configs/Replica/room0.yaml gives."""
+        t, m = cfg["tracking"], cfg["mapping"]
+        w = ("w_sdf_fs", "w_sdf_center", "w_sdf_tail", "w_depth", "w_color")
+        return cls(tracking_pixels=int(t["pixels"]), tracking_iters=int(t["iters"]),
+                   ignore_edge_H=int(t["ignore_edge_H"]), ignore_edge_W=int(t["ignore_edge_W"]),
+                   lr_T=float(t["lr_T"]), lr_R=float(t["lr_R"]), const_speed_assumption=bool(t["const_speed_assumption"]),
+                   tracking_w=tuple(float(t[k]) for k in w),
+                   mapping_pixels=int(m["pixels"]), iters_first=int(m["iters_first"]), iters=int(m["iters"]),
+                   every_frame=int(m["every_frame"]), keyframe_every=int(m["keyframe_every"]),
+                   mapping_window_size=int(m["mapping_window_size"]), joint_opt=bool(m["joint_opt"]),
+                   joint_opt_cam_lr=float(m["joint_opt_cam_lr"]), lr_first_factor=float(m["lr_first_factor"]),
+                   lr_factor=float(m["lr_factor"]), decoders_lr=float(m["lr"]["decoders_lr"]),
+                   planes_lr=float(m["lr"]["planes_lr"]), c_planes_lr=float(m["lr"]["c_planes_lr"]),
+                   mapping_w=tuple(float(m[k]) for k in w), mixed_precision=bool(cfg.get("mixed_precision", False)))
+
 
 class HipBackend:
     """The product path.  (tests/ provides the same interface over the CPU oracle.)"""

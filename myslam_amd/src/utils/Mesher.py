@@ -1,6 +1,7 @@
 """The reference's Mesher (src/utils/Mesher.py) on the HIP path: the field query, the frame hull and mesh extraction.
 
-Functions with the reference's signatures, to be bound onto its Mesher class one line each:
+The `Mesher` class below has the reference's constructor and these functions as its methods.  The functions keep the
+reference's signatures and can also be bound onto the reference's own Mesher class one line each:
 
     from myslam_amd.src.utils import Mesher as hip_mesher
     Mesher.eval_points = hip_mesher.eval_points                        # Mesher.py:130-157
@@ -210,6 +211,33 @@ def get_mesh(self, mesh_out_file, all_planes, decoders, keyframe_dict, device='c
         print(NO_SURFACE)
         return
     write_ply(mesh_out_file, *m)
+
+
+class Mesher:
+    """The reference's class (src/utils/Mesher.py:42-61) over the functions above: same constructor, the attributes those
+    functions read, the functions as its methods.  `eslam` provides bound, H, W, fx, fy, cx, cy (after update_cam) and,
+    optionally, renderer and verbose.  The reference's constructor also opens a second dataset reader that none of its
+    methods uses; that is left out."""
+
+    def __init__(self, cfg, args, eslam, points_batch_size=500000, ray_batch_size=100000):
+        self.points_batch_size = points_batch_size
+        self.ray_batch_size = ray_batch_size
+        self.renderer = getattr(eslam, 'renderer', None)
+        self.scale = cfg['scale']
+        self.resolution = cfg['meshing']['resolution']
+        self.level_set = cfg['meshing']['level_set']
+        self.mesh_bound_scale = cfg['meshing']['mesh_bound_scale']
+        self.bound = eslam.bound
+        self.verbose = getattr(eslam, 'verbose', False)
+        self.marching_cubes_bound = torch.from_numpy(np.array(cfg['mapping']['marching_cubes_bound']) * self.scale)
+        self.H, self.W, self.fx, self.fy, self.cx, self.cy = eslam.H, eslam.W, eslam.fx, eslam.fy, eslam.cx, eslam.cy
+
+    eval_points = eval_points
+    keyframe_points = keyframe_points
+    get_bound_from_frames = get_bound_from_frames
+    get_bound_from_frames_tsdf = get_bound_from_frames_tsdf
+    extract_mesh = extract_mesh
+    get_mesh = get_mesh
 
 
 def write_ply(path, vertices, faces, colors=None):

@@ -2,7 +2,8 @@
 (`get_dataset`, `SeqSampler`, `BaseDataset`, `Replica`, `ScanNet`, `TUM_RGBD`; `readEXR_onlydepth` is named but
 not built: no OpenEXR here and no shipped configuration uses it), with PIL + numpy + torch instead of OpenCV (cv2 is not
 available in this image).  Host code: the callers either side of the hot path need it to
-feed real sequences to the tracking / mapping loops; nothing here touches the GPU kernels.
+feed real sequences to the tracking / mapping loops.  The readers themselves touch no GPU kernel; `FrameStream` at the
+end of the file delivers their items prepared on the device instead (ops.prepare_frame), decoded ahead by threads.
 
 Item: `(index, color [H',W',3] float RGB in [0,1], depth [H',W'] float32 metres * scale, c2w [4,4] float32)` after the
 optional resize to `crop_size` and the `crop_edge` crop (datasets.py:88-114).
@@ -48,13 +49,13 @@ def _imread_depth(path):
     return a
 
 
-def undistort(color, K, dist):
-    """cv2.undistort(color, K, dist) restated: for every pixel of the OUTPUT (undistorted, same K) image, where the
-    distorted input image shows the same ray, sampled bilinearly, 0 outside.  dist = (k1, k2, p1, p2[, k3])."""
+def undistort_map(K, dist, H, W):
+    """Where every pixel of the undistorted H x W image (same K) lies in the distorted one: float32 [H,W,2], (x, y) in
+    F.grid_sample's [-1, 1] coordinates with aligned corners.  dist = (k1, k2, p1, p2[, k3]).  Depends on the camera only:
+    computed once per dataset by FrameSpec."""
     d = np.zeros(5, dtype=np.float64)
     d[:min(5, len(dist))] = np.asarray(dist, dtype=np.float64).reshape(-1)[:5]
     k1, k2, p1, p2, k3 = d
-    H, W = color.shape[:2]
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
     x, y = (u - cx) / fx, (v - cy) / fy
@@ -63,7 +64,14 @@ def undistort(color, K, dist):
     xd = x * radial + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
     yd = y * radial + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
     mu, mv = fx * xd + cx, fy * yd + cy
-    grid = torch.from_numpy(np.stack([2 * mu / (W - 1) - 1, 2 * mv / (H - 1) - 1], -1)).float()[None]
+    return torch.from_numpy(np.stack([2 * mu / (W - 1) - 1, 2 * mv / (H - 1) - 1], -1)).float()
+
+
+def undistort(color, K, dist):
+    """cv2.undistort(color, K, dist) restated: for every pixel of the OUTPUT (undistorted, same K) image, where the
+    distorted input image shows the same ray (undistort_map), sampled bilinearly, 0 outside."""
+    H, W = color.shape[:2]
+    grid = undistort_map(K, dist, H, W)[None]
     img = torch.from_numpy(np.array(color)).permute(2, 0, 1)[None].float()
     out = F.grid_sample(img, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0].permute(1, 2, 0)
     return out.round().clamp(0, 255).to(torch.uint8).numpy() if color.dtype == np.uint8 else out.numpy()
@@ -166,14 +174,20 @@ class BaseDataset(Dataset):
     def __len__(self):
         return self.n_img
 
-    def __getitem__(self, index):
-        K_dist = None
-        if self.distortion is not None:
-            K_dist = (as_intrinsics_matrix([self.fx, self.fy, self.cx, self.cy]), self.distortion)
-        color, depth = _load_rgbd(self.color_paths[index], self.depth_paths[index], self.png_depth_scale, K_dist)
+    def _K_dist(self):
+        if self.distortion is None:
+            return None
+        return as_intrinsics_matrix([self.fx, self.fy, self.cx, self.cy]), self.distortion
+
+    def images(self, index):
+        """The frame's colour [H',W',3] float64 and depth [H',W'] float32 (no pose: reading them changes nothing)."""
+        color, depth = _load_rgbd(self.color_paths[index], self.depth_paths[index], self.png_depth_scale, self._K_dist())
         color = _match_size(color, depth.shape)
         color, depth = _resize_pair(color, depth * self.scale, self.crop_size)
-        color, depth = _trim(color, depth, self.crop_edge)
+        return _trim(color, depth, self.crop_edge)
+
+    def __getitem__(self, index):
+        color, depth = self.images(index)
         # the stored pose itself is scaled, in place, as the reference does it: an item read twice is scaled twice when
         # scale != 1 (every config of the reference has scale 1)
         c2w = self.poses[index]
@@ -294,6 +308,155 @@ class TUM_RGBD(BaseDataset):
         world = self.pose_matrices(gt[[k for _, _, k in kept], 1:].astype(np.float64))
         rebased = np.stack([np.eye(4)] + [m for m in np.linalg.inv(world[0]) @ world[1:]])
         return images, depths, _to_renderer_frame(rebased)
+
+
+# ---- frames prepared on the device ---------------------------------------------------------------------------------
+class FrameSpec:
+    """What ops.prepare_frame needs to know about a dataset, made once: the depth scales, crop_size, crop_edge and, for a
+    camera with lens distortion, the undistortion map (float32 [H,W,2], uploaded once per device)."""
+
+    def __init__(self, png_depth_scale, scale=1.0, crop_size=None, crop_edge=0, grid=None):
+        self.png_depth_scale, self.scale = float(png_depth_scale), float(scale)
+        self.crop_size = None if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+        self.crop_edge = int(crop_edge)
+        self.grid = grid
+        self._grid_on = {}
+
+    @classmethod
+    def from_reader(cls, reader):
+        grid = None
+        if reader.distortion is not None:
+            K = as_intrinsics_matrix([reader.fx, reader.fy, reader.cx, reader.cy])
+            grid = undistort_map(K, reader.distortion, int(reader.H), int(reader.W))
+        return cls(reader.png_depth_scale, reader.scale, reader.crop_size, reader.crop_edge, grid)
+
+    def grid_on(self, device):
+        device = torch.device(device)
+        g = self._grid_on.get(device)
+        if g is None and self.grid is not None:
+            g = self._grid_on[device] = self.grid.contiguous().to(device)
+        return g
+
+
+class FrameStream:
+    """Iterator of (idx, colour [H',W',3] float32, depth [H',W'] float32, c2w [4,4] float32) on `device`: the tuples
+    Slam.run takes, the items of `reader` (a BaseDataset) with the per-frame arithmetic done by ops.prepare_frame.
+
+    Decoding (PIL; it releases the GIL) runs up to `prefetch` frames ahead on at most 4 background threads, which copy the
+    decoded pair into pinned staging buffers and touch no device API.  The consumer's thread uploads and prepares every
+    decoded frame on a side stream each time it takes a frame, and its stream waits on the frame's event at hand-over, so
+    upload and preparation of the frames ahead run beside the loop's work.  prefetch=0: the same path, inline.  Poses are scaled once, on a copy (BaseDataset scales the stored pose in place at
+    every read).  native=False: the host reader's items, uploaded as they are (colour cast to float32) - the path this
+    class replaces, kept for comparison and timing."""
+
+    MAX_THREADS = 4
+
+    def __init__(self, reader, device, prefetch=2, native=True):
+        self.reader, self.device = reader, torch.device(device)
+        self.prefetch, self.native = max(0, int(prefetch)), bool(native)
+        self.spec = FrameSpec.from_reader(reader)
+        self.n_img = len(reader)
+        self._poses = None
+        self._side = None
+
+    def __len__(self):
+        return self.n_img
+
+    def poses(self):
+        """The reader's poses with the translation scaled, as device tensors (a copy: the reader's own stay untouched)."""
+        if self._poses is None:
+            out = []
+            for p in self.reader.poses[:self.n_img]:
+                q = p.clone()
+                q[:3, 3] *= self.spec.scale
+                out.append(q.to(self.device))
+            self._poses = out
+        return self._poses
+
+    # ---- host half: files -> pinned staging buffers (a background thread; touches no device API) ----
+    def _decode(self, k, slot):
+        rgb = _imread_color(self.reader.color_paths[k])
+        dep = _imread_depth(self.reader.depth_paths[k])
+        if dep.dtype != np.uint16:
+            raise ValueError(f"{self.reader.depth_paths[k]}: expected 16-bit depth samples, got {dep.dtype}")
+        pair = {"rgb": rgb, "dep": dep.view(np.int16)}
+        if all(key in slot and tuple(slot[key].shape) == a.shape for key, a in pair.items()):
+            self._stage(slot, pair)
+            return slot, None
+        return slot, pair                                # first use of the slot (or a new size): staged by the consumer
+
+    @staticmethod
+    def _stage(slot, pair):
+        for key, a in pair.items():
+            if key not in slot or tuple(slot[key].shape) != a.shape:
+                slot[key] = torch.empty(a.shape, dtype=torch.uint8 if key == "rgb" else torch.int16).pin_memory()
+            slot[key].numpy()[...] = a
+
+    # ---- device half: upload and prepare on the side stream (the consumer's thread) ----
+    def _upload(self, decoded):
+        from ... import ops
+        slot, pair = decoded
+        if pair is not None:
+            self._stage(slot, pair)                      # (allocates the slot's pinned buffers: this thread's job)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            rgb = slot["rgb"].to(self.device, non_blocking=True)
+            dep = slot["dep"].to(self.device, non_blocking=True)
+            slot["event"].record(self._side)             # the staging buffers are free again after this point
+            color, depth = ops.prepare_frame(rgb, dep, self.spec)
+            ready = torch.cuda.Event()
+            ready.record(self._side)
+        return color, depth, ready
+
+    def _host_item(self, k, pose):
+        color, depth = self.reader.images(k)
+        return k, color.float().to(self.device), depth.to(self.device), pose
+
+    def __iter__(self):
+        poses = self.poses()
+        if not self.native:
+            for k in range(self.n_img):
+                yield self._host_item(k, poses[k])
+            return
+        if not torch.cuda.is_available() or self.device.type != "cuda":
+            raise RuntimeError("FrameStream(native=True) prepares frames on the GPU; there is no CPU fallback")
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        ahead = self.prefetch
+        slots = [{"event": torch.cuda.Event()} for _ in range(ahead + 1)]
+        if ahead == 0:
+            for k in range(self.n_img):
+                slots[0]["event"].synchronize()          # the upload that last read the staging buffers has finished
+                yield self._hand_over(k, self._upload(self._decode(k, slots[0])), poses[k])
+            return
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(max_workers=min(self.MAX_THREADS, ahead), thread_name_prefix="frames")
+        try:
+            decoding, uploaded = {}, {}
+            nxt = 0
+            for k in range(self.n_img):
+                # frames k .. k + prefetch are in flight, each in a staging slot of its own; a slot is decoded into again
+                # only after the frame that held it was handed over and its upload has finished
+                while nxt < self.n_img and nxt <= k + ahead:
+                    slot = slots[nxt % len(slots)]
+                    slot["event"].synchronize()
+                    decoding[nxt] = pool.submit(self._decode, nxt, slot)
+                    nxt += 1
+                # every frame already decoded goes to the side stream now, so that its upload and preparation run beside
+                # the loop's work on frame k; all device work is issued from this thread
+                for j in sorted(decoding):
+                    if j == k or decoding[j].done():
+                        uploaded[j] = self._upload(decoding.pop(j).result())
+                yield self._hand_over(k, uploaded.pop(k), poses[k])
+        finally:
+            pool.shutdown(wait=True, cancel_futures=True)
+
+    def _hand_over(self, k, item, pose):
+        color, depth, ready = item
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ready)
+        color.record_stream(cur)                         # allocated on the side stream, used (and freed) on this one
+        depth.record_stream(cur)
+        return k, color, depth, pose
 
 
 dataset_dict = {
