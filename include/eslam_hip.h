@@ -572,6 +572,12 @@ int eslam_deterministic(void);
  * or of n free points (render == 0, S ignored): 2048, except in the default mode for batches that would make fewer than 192
  * workgroups of 2048 samples.  Host arithmetic only, no launch; 0 for an empty or invalid batch. */
 int eslam_scatter_bundle_samples(int64_t n, int S, int render);
+/* Which pair of kernels the last eslam_render_bwd / eslam_render_bwd_loss / eslam_decode_bwd of this process dispatched:
+ * 1 = the rank-16 pair (float32 planes with gradients, rays without position gradients, not deterministic mode: the decoder
+ * backward stores the 16-wide hidden gradient, the scatter expands it per cell), 0 = full-width feature-gradient rows.
+ * Host bookkeeping, no launch.  FOR TESTS ONLY: one unsynchronised process-wide value written at dispatch - with concurrent
+ * callers it is racy and names only the last dispatch; no caller may branch on it. */
+int eslam_last_backward_rank16(void);
 
 /* Host-side helper of the Python layer (no reference counterpart): `waiter` waits for the work enqueued on `signaler` so
  * far - the fork / join of the side stream the ray ordering (eslam_ray_order, what the backward's scatter bundles by) runs

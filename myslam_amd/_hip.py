@@ -130,6 +130,7 @@ SIGNATURES = {
     "eslam_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_deterministic": (_i, []),
     "eslam_scatter_bundle_samples": (_i, [_i64, _i, _i]),
+    "eslam_last_backward_rank16": (_i, []),
     "eslam_loss_scratch_floats": (_i64, [_i64]),
     "eslam_loss_scratch_reset": (_i, [_vp, _i64, _vp]),
     "eslam_loss_value": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp]),

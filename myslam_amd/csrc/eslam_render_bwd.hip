@@ -107,7 +107,13 @@ struct RayBwdIn {                  // MODE >= 1: what the composite backward of 
 // MODE 0 with LOWP (free points, eslam_decode_bwd on half copies; saved features bf16): WGRAD 159 VGPRs and 66.6 KB of LDS -
 // two workgroups per CU, i.e. the 2 waves per SIMD of the bound, are what the LDS allows; frozen decoders 90 VGPRs, 15 KB,
 // 5 waves per SIMD (the bound is a floor).  Neither uses scratch.
-template <int MODE, bool WGRAD, bool LOWP>
+// GZ (float32 rays whose positions need no gradient, plane gradients wanted, not deterministic): the features' gradient is
+// g_feat = W1^T . g_z1 and has rank 16, and the scatter is linear - so the product is NOT formed here (16 of a block's 76
+// dependent MFMAs, 12 of its 16 ds_bpermute, three of its four 16-byte stores per lane: what is left is the move of g_z1's four
+// registers to the gather role and one store).  The block's g_z1 is stored, gz[2][N][16]
+// (decoder-major: a 128-byte line holds two consecutive samples of one ray), in the region g_feat occupies otherwise and a
+// quarter of its size; scatter_sort_kernel<GZ> sums it per texel cell and expands each cell's sums once.
+template <int MODE, bool WGRAD, bool LOWP, bool GZ = false>
 __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t dec, const float* __restrict__ feat,
                                                       const float* __restrict__ g_o, int64_t N,
                                                       float* __restrict__ g_feat, float* __restrict__ slabs,
@@ -121,6 +127,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     else stage_decoder_weights(wlds, dec, threadIdx.x, blockDim.x);
     __syncthreads();
 
+    static_assert(!GZ || (!LOWP && MODE != 0), "GZ: float32 rays only");
     const int d = blockIdx.y;                         // 0 = sdf decoder, 1 = colour decoder
     const int nout = d ? 3 : 1;
     const float* L = wlds + d * DEC_LDS;
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
         w2t[ks] = L[DEC_W2 + (4 * q + ks) * 16 + r];            // W2[j = 4q+ks][k' = r]
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb)                          // row r of row block mb <-> feature (mb>>1)*32 + 16*(mb&1) + r:
-            w1t[mb][ks] = L[DEC_W1 + (4 * q + ks) * 64 + (mb >> 1) * 32 + 16 * (mb & 1) + r];   // lane q then holds piece q
+            if (!GZ) w1t[mb][ks] = L[DEC_W1 + (4 * q + ks) * 64 + (mb >> 1) * 32 + 16 * (mb & 1) + r];   // lane q then holds piece q
     }
     }
 
@@ -167,12 +174,21 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     float gbeta_acc = 0.0f;
 
     typedef unsigned uint4_t __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t gfrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g_feat, 0, (int)((unsigned)N * 512u), 0x00020000);
-    // four stores the hardware drops (offsets beyond the descriptor's range; distinct, so that none is eliminated): they put
-    // "exactly four stores are younger than every load issued before" into the compiler's picture where a loop is entered
+    const __amdgpu_buffer_rsrc_t gfrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g_feat, 0, (int)((unsigned)N * (GZ ? 128u : 512u)), 0x00020000);
+    // as many stores as a block issues - four, GZ: one - that the hardware drops (offsets beyond the descriptor's range; distinct,
+    // so that none is eliminated): they put "exactly four (GZ: one) stores are younger than every load issued before" into the
+    // compiler's picture where a loop is entered
     auto dropped_stores = [&]() {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) __builtin_amdgcn_raw_buffer_store_b128((uint4_t){0u, 0u, 0u, 0u}, gfrsrc, (int)(0xFFFFFF00u + 16u * j), 0, 0);
+        for (int j = 0; j < (GZ ? 1 : 4); ++j) __builtin_amdgcn_raw_buffer_store_b128((uint4_t){0u, 0u, 0u, 0u}, gfrsrc, (int)(0xFFFFFF00u + 16u * j), 0, 0);
+    };
+    // GZ: the block's g_z1 rows, gather role: lane (point gp, piece gq) holds hidden units 4gq..4gq+3, so a quad of lanes writes
+    // one point's 64 contiguous bytes with ONE 16-byte store per lane, ALWAYS issued; 2 N * 64 < 2^32 - 256 follows from the
+    // launch's check of N * 512
+    const unsigned gz_base = (unsigned)d * ((unsigned)N * 64u);
+    auto store_gz = [&](const int64_t p0, const int b, const int nvalid, const float gzr[4]) {
+        const unsigned off = (16 * b + gp < nvalid) ? (unsigned)(p0 + 16 * b + gp) * 64u + gz_base + (unsigned)(gq * 16) : 0xFFFFFF00u;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, (float4_t){gzr[0], gzr[1], gzr[2], gzr[3]}), gfrsrc, (int)off, 0, 0);
     };
     // the block's feature-gradient rows, gather role: four 16-byte stores per lane (both tiles: piece j at byte 64 j of the
     // decoder's half row), ALWAYS issued; N * 512 < 2^32 - 256 is checked at the launch
@@ -215,7 +231,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
         // gather role: the 16 features of point 16b + gp, piece gq.  The rows of block b+1 are requested before block b is
         // computed: at 2 waves per SIMD nothing else hides the ~2k-cycle load latency.
         // A wave's loads and stores retire in order on ONE counter (vmcnt).  A block's rows are requested a block ahead, i.e.
-        // BEFORE the previous block's four feature-gradient stores, so "all but the 4 youngest operations have retired" is all
+        // BEFORE the previous block's four feature-gradient stores (GZ: its one g_z1 store; read 1 for 4 below), so "all but the 4
+        // youngest operations have retired" is all
         // the top of a block has to wait for - but the compiler can only say so if it can COUNT the stores: as predicated
         // global stores behind a branch (rows past the tile's end) it cannot, waits for vmcnt(0), and every block - and every
         // ray's first use of its prefetched inputs - sat out the store acknowledgement of the block before (~2 k and ~5 k
@@ -235,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             // the same rows again in the "feature on the lane" layout of the g_W1 contraction (B operand): NOT re-read from
             // memory but handed over through a wave-private LDS tile, written here in the gather role and read back just before
             // the contraction.  A global re-read (L1 / L2 hits) was waited for in the middle of the block - behind the previous
-            // block's four feature-gradient stores, a wave's loads and stores retiring in order - which exposed those stores'
+            // block's four feature-gradient stores (GZ: one), a wave's loads and stores retiring in order - which exposed those stores'
             // latency in every block (15 us of this kernel at 4096 x 64).
             float4_t fbk[4];
             short4_t fbkp[4];
@@ -307,6 +324,11 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             gb1 += gz1;
             gb2 += gz2;
 
+            if (GZ) {       // MFMA-role lane (r, q) holds rows 4q..4q+3 of point r: to the gather role, one store
+                float gzr[4] = {gz1[0], gz1[1], gz1[2], gz1[3]};
+                to_gather_role<true, 4>(gzr, lane);
+                store_gz(p0, b, nvalid, gzr);
+            } else {
             // g_feat^T = W1^T . g_z1^T, four row blocks ordered so that MFMA-role lane (r, q) receives piece q of point r
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
@@ -318,6 +340,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             }
             to_gather_role<true, 16>(gf, lane);
             store_rows(p0, b, nvalid, gf);
+            }
             }
             if (!WGRAD) continue;
 
@@ -469,7 +492,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
         for (; ray < R; ray += stride) {
             const int64_t base = (int64_t)ray * S;
             // What is requested ahead - this ray's scalars and its last chunk a ray ago, a further chunk a tile ago - is waited
-            // for HERE, in front of the next requests and behind the four stores that ended the tile in between: vmcnt(4).
+            // for HERE, in front of the next requests and behind the four stores that ended the tile in between: vmcnt(4)
+            // (GZ: one store, vmcnt(1)).
             // (Waited for at its first use further down, the wait would cover the requests issued meanwhile as well - the
             // compiler cannot count those: optional pointers, rows past S - and expose their whole latency in every ray:
             // 5.5 k cycles of a ray's ~30 k, profiles/r02/t_*.)
@@ -888,13 +912,13 @@ static Bound make_bound(const float* b6) {
 
 int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float* rays_o, const float* rays_d,
                      const float* z_or_pts, int64_t R, int S, bool render, const float* g_feat, const int* perm,
-                     hipStream_t st, const DecReduceArgs* red);
+                     hipStream_t st, const DecReduceArgs* red, const eslam_decoders_t* gz_dec);
 bool eslam_scatter_can_reduce(bool render);
 
 
 static int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
-// workspace layout: g_o [n,4] | g_feat [n,128] | slabs [MLP_BWD_MAX_WG*4][2][SLAB] + g_beta partials [n/4 + 1] |
+// workspace layout: g_o [n,4] | g_feat [n,128] (rank-16 path: g_z1 [2][n,16] in its first quarter) | slabs [MLP_BWD_MAX_WG*4][2][SLAB] + g_beta partials [n/4 + 1] |
 //                   ray order [n] (int)
 static int64_t slab_region_bytes(int64_t n_points) {
     return ((int64_t)MLP_BWD_MAX_WG * 4 * 2 * SLAB + n_points / 4 + 1) * 4;      // (g_beta partials need MLP_BWD_MAX_WG only)
@@ -905,6 +929,10 @@ extern "C" int64_t eslam_bwd_workspace_bytes(int64_t n_points) {
     return align256(n_points * 4 * 4) + align256(n_points * 128 * 4) +
            align256(slab_region_bytes(n_points)) + align256(n_points * 4);
 }
+
+// 1 when the last backward this process dispatched took the rank-16 pair, 0 when it wrote full-width rows (host bookkeeping)
+static int g_last_backward_rank16 = 0;
+extern "C" int eslam_last_backward_rank16(void) { return g_last_backward_rank16; }
 
 // mode 0: free points (g_o in the workspace); 1: rays, upstream gradients in rb; 2: rays, mapping-loss gradients from li
 static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, const Bound& bnd, const float* rays_o,
@@ -929,12 +957,30 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
         return 1;
     }
     eslam_prof_begin(PROF_MLP_BWD, st);
-#define LAUNCH_MB(MD, WG, LP) \
-    hipLaunchKernelGGL((mlp_bwd_kernel<MD, WG, LP>), dim3(nwg, 2), dim3(256), 0, st, *dec, feat, g_o, N, g_feat, slabs, rb, \
+#define LAUNCH_MB(MD, WG, LP, ...) \
+    hipLaunchKernelGGL((mlp_bwd_kernel<MD, WG, LP, ##__VA_ARGS__>), dim3(nwg, 2), dim3(256), 0, st, *dec, feat, g_o, N, g_feat, slabs, rb, \
                        li ? *li : none)
     const int lowp = eslam_planes_lowp(planes);
     if (lowp < 0) return 1;
-    if (lowp) {
+    bool any_grad = false, all_grad = true;
+    for (int i = 0; i < NPL; ++i) {
+        any_grad |= planes[i].grad != nullptr;
+        all_grad &= planes[i].grad != nullptr;
+    }
+    if (any_grad && !all_grad) {
+        eslam_set_error("plane gradients must be requested for all 12 planes or for none");
+        return 1;
+    }
+    // The rank-16 pair (mlp_bwd_kernel<GZ> writes g_z1, scatter_sort_kernel<GZ> expands per cell): float32 rays whose
+    // feature gradients only the scatter reads.  Position gradients (coord_bwd_kernel reads full rows), free points, the
+    // mixed-precision kernels and deterministic mode (fixed point per CONTRIBUTION) keep the full-width rows.
+    const bool gz = !lowp && render && any_grad && !g_out_a && !eslam_deterministic();
+    g_last_backward_rank16 = gz ? 1 : 0;
+    if (gz) {
+        if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, false, true); else LAUNCH_MB(1, false, false, true); }
+        else { if (g_dec) LAUNCH_MB(2, true, false, true); else LAUNCH_MB(2, false, false, true); }
+    }
+    else if (lowp) {
         if (mode == 0) { if (g_dec) LAUNCH_MB(0, true, true); else LAUNCH_MB(0, false, true); }      // feat: [N,128] bf16
         else if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, true); else LAUNCH_MB(1, false, true); }
         else { if (g_dec) LAUNCH_MB(2, true, true); else LAUNCH_MB(2, false, true); }
@@ -946,15 +992,6 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     eslam_prof_end(PROF_MLP_BWD, st);
     if (int rc = eslam_check_launch("mlp_bwd_kernel")) return rc;
     const int n_beta_parts = render ? nwg : 0;
-    bool any_grad = false, all_grad = true;
-    for (int i = 0; i < NPL; ++i) {
-        any_grad |= planes[i].grad != nullptr;
-        all_grad &= planes[i].grad != nullptr;
-    }
-    if (any_grad && !all_grad) {
-        eslam_set_error("plane gradients must be requested for all 12 planes or for none");
-        return 1;
-    }
     DecReduceArgs red = {};
     red.slabs = slabs; red.nrows = nwg; red.g_dec = g_dec;
     red.beta_parts = render ? beta_parts : nullptr; red.n_beta_parts = n_beta_parts; red.g_beta = g_beta;
@@ -974,7 +1011,8 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     // plane gradients
     if (any_grad) {
         eslam_prof_begin(PROF_SCATTER, st);
-        if (int rc = eslam_scatter_v2(planes, bnd, rays_o, rays_d, z_or_pts, R, S, render, g_feat, perm, st, fold ? &red : nullptr))
+        if (int rc = eslam_scatter_v2(planes, bnd, rays_o, rays_d, z_or_pts, R, S, render, g_feat, perm, st, fold ? &red : nullptr,
+                                      gz ? dec : nullptr))
             return rc;
         eslam_prof_end(PROF_SCATTER, st);
     }

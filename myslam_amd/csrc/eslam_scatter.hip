@@ -326,8 +326,14 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
 // adjacent cells det_bad moves to the lower half-wave together with the carried column, so it never reaches a texel the
 // contribution did not touch).  A texel's SUM that leaves +-5.2e5 while every contribution is in range wraps undetected.
 struct ShadowOff { int64_t o[NPL]; };
+// GZ (the rank-16 path, see mlp_bwd_kernel): g_feat holds gz[2][N][16], the gradient at the decoders' first hidden layer, and
+//   the features' gradient W1^T . g_z1 is never formed per sample.  The walk sums w * g_z1 per cell in the 16-wide space - lane
+//   (hx = lane >> 5, row = (lane >> 4) & 1, j = lane & 15), ONE accumulator, one 64-byte row per entry shared by the six planes of
+//   a decoder - and the flush multiplies the cell's 2 x 2 x 16 sums by the plane's [16, 32] slice of W1 (LDS, staged once per
+//   workgroup) before the same two atomics per lane (hx, c).  tests/rank16_ref.py restates the bookkeeping in numpy.
 constexpr int SC_NT = 512;
-template <bool RENDER, bool DET, int SPT = 4>
+constexpr int GZ_WP = 20;                           // pitch (floats) of the W1 slice's rows [c][j]: 16-byte aligned, conflict-free
+template <bool RENDER, bool DET, int SPT = 4, bool GZ = false>
 __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet planes, const Bound bnd,
                                                           const float* __restrict__ rays_o,
                                                           const float* __restrict__ rays_d,
@@ -335,8 +341,10 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
                                                           const int* __restrict__ perm, int R, int S,
                                                           const float* __restrict__ g_feat, int bundle, int nbundles,
                                                           long long* __restrict__ shadow,
-                                                          const ShadowOff shoff, const DecReduceArgs red, const int red_blocks) {
+                                                          const ShadowOff shoff, const DecReduceArgs red, const int red_blocks,
+                                                          const float* __restrict__ gz_w1_sdf, const float* __restrict__ gz_w1_rgb) {
     constexpr int NT = SC_NT;
+    static_assert(!GZ || (RENDER && !DET), "GZ: the float render path only");
     constexpr int BM = SPT * NT;                       // SPT samples per thread in the cell / sort phases
     constexpr int CH = WAVE * SPT;                     // sorted entries a wave walks
     static_assert(SPT == 2 || SPT == 4, "samples per thread");
@@ -351,6 +359,10 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     //   sgrow [BM] row of g_feat (global point index)
     // The sort phases use the same memory differently (see below).
     __shared__ __attribute__((aligned(16))) unsigned lds_raw[6 * BM];
+    // GZ: + 2560 B for the plane's slice of W1 as [c][j] and + 2048 B of wave-private exchange (a cell's 64 sums): 53 760 B at
+    // BM = 2048, three workgroups per CU as before
+    __shared__ __attribute__((aligned(16))) float gz_w[GZ ? ESLAM_C_DIM * GZ_WP : 4];
+    __shared__ __attribute__((aligned(16))) float gz_a[GZ ? NT : 4];
     float4_t* const sw = (float4_t*)lds_raw;
     unsigned* const sxy = lds_raw + 4 * BM;
     int* const sgrow = (int*)(lds_raw + 5 * BM);
@@ -404,6 +416,10 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     if (bidx >= nbundles || pi >= NPL) return;
     const int d = pi / 6, o = (pi % 6) >> 1, lvl = pi & 1;
     const eslam_plane_t& P = planes.p[pi];
+    // GZ: thread (j, c) fetches W1[j][lvl * 32 + c] of the plane's decoder now and stores it behind the cell phase's own loads
+    float gz_wv = 0.0f;
+    if (GZ) gz_wv = (d ? gz_w1_rgb : gz_w1_sdf)[(threadIdx.x >> 5) * ESLAM_FEAT + lvl * ESLAM_C_DIM + (threadIdx.x & 31)];
+    static_assert(!GZ || NT == ESLAM_HIDDEN * ESLAM_C_DIM, "one element of the slice per thread");
     const int pw = P.w, ph = P.h;
     const int psy = (int)P.stride_y, psx = (int)P.stride_x, psc = (int)P.stride_c;
     float* __restrict__ grad = P.grad;
@@ -451,6 +467,7 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
             }
         }
     }
+    if (GZ) gz_w[(threadIdx.x & 31) * GZ_WP + (threadIdx.x >> 5)] = gz_wv;      // read in the walk, many barriers from here
     bx0 = wave_min_i(bx0); bx1 = wave_max_i(bx1);
     by0 = wave_min_i(by0); by1 = wave_max_i(by1);
     if (lane == 0) {
@@ -621,7 +638,8 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     // issue-bound.  The g_feat values of WALK_N entries are loaded ahead of the walk of the
     // previous WALK_N: a wave's loads, stores and atomics retire in order on one vmcnt counter, so a load issued BEHIND an
     // atomic would wait for it (~3000 cycles under load).
-    const char* __restrict__ gcol = (const char*)(g_feat + d * 64 + lvl * 32);     // + row * 512 + c * 4 bytes
+    const char* __restrict__ gcol = GZ ? (const char*)(g_feat + (size_t)d * (size_t)npts * 16)      // + row * 64 + j * 4 bytes
+                                       : (const char*)(g_feat + d * 64 + lvl * 32);                 // + row * 512 + c * 4 bytes
     unsigned cur_xy = PAD_XY;                  // cell being accumulated (PAD_XY: none / padding, never flushed)
     unsigned last_xy = PAD_XY;                 // xy of the last entry of the previous block
     typedef typename std::conditional<DET, long long, float>::type acc_t;
@@ -636,14 +654,41 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     const unsigned lane_off = (unsigned)(c * psc) << 2;
     const unsigned dm_bytes = (unsigned)(swap ? psy : psx) << 2, dM_bytes = (unsigned)(swap ? psx : psy) << 2;
     char* __restrict__ gbytes = DET ? (char*)(shadow + shoff.o[pi]) : (char*)grad;
+    float* const gz_as = gz_a + (GZ ? wave * WAVE : 0);
     auto flush = [&](bool lower_half_only) {
         if (cur_xy != PAD_XY) {
+            acc_t f0 = acc0, f1 = acc1;                       // what the lane adds (GZ: acc0 itself stays: it may be carried)
+            if (GZ) {
+                // the cell's 64 sums A[hx][row][j] (one per lane) -> lane (hx, c): sum_j W1[j][c] A[hx][row][j] for rows 0 and 1,
+                // through the wave's 256 bytes of LDS (a half-wave reads ONE address: broadcast) and the slice's row c
+                gz_as[lane] = (float)acc0;
+                WAVE_SYNC();
+                const float4_t* const A = (const float4_t*)(gz_as + hx * 32);
+                // (the slice's row is read anew in every flush: as a loop invariant the compiler keeps its 16 values in registers -
+                // 86 VGPRs, 5 waves per SIMD - so the row's offset is made opaque to it)
+                unsigned wrow = (unsigned)(c * GZ_WP);
+                asm volatile("" : "+v"(wrow));
+                const float4_t* const Wc = (const float4_t*)(gz_w + wrow);
+                float r0 = 0.0f, r1 = 0.0f;
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    const float4_t a0 = A[jj], a1 = A[4 + jj], wv = Wc[jj];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { r0 += wv[i] * a0[i]; r1 += wv[i] * a1[i]; }
+                    // two halves of six reads, each summed where it stands: all twelve in flight (the compiler moves the sums behind
+                    // the lower-half-only flush's lane test) take 48 registers - 86 VGPRs in all, 5 waves per SIMD
+                    if (jj & 1) asm volatile("" : "+v"(r0), "+v"(r1));
+                }
+                WAVE_SYNC();                                  // (the next flush's write stays behind these reads)
+                f0 = (acc_t)r0;
+                f1 = (acc_t)r1;
+            }
             const unsigned o0 = (cur_xy & ~3u) + lane_off + ((cur_xy & 1u) & (unsigned)hx) * dm_bytes;
             const unsigned o1 = o0 + ((cur_xy >> 1) & 1u) * dM_bytes;
             if (DET) {
                 if (!lower_half_only || hx == 0) {           // the shadow mirrors the plane element for element: 8 bytes each
-                    atomicAdd((unsigned long long*)(gbytes + 2 * (size_t)o0), (unsigned long long)acc0);
-                    atomicAdd((unsigned long long*)(gbytes + 2 * (size_t)o1), (unsigned long long)acc1);
+                    atomicAdd((unsigned long long*)(gbytes + 2 * (size_t)o0), (unsigned long long)f0);
+                    atomicAdd((unsigned long long*)(gbytes + 2 * (size_t)o1), (unsigned long long)f1);
                     // a contribution that was NaN / Inf or beyond the fixed-point range (|g w| >= 2.6e5; __float2ll_rn would
                     // have saturated or wrapped it silently): poison the float gradient so that divergence stays visible
                     if (det_bad) {
@@ -652,8 +697,8 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
                     }
                 }
             } else if (!lower_half_only || hx == 0) {
-                atomicAdd((float*)(gbytes + o0), (float)acc0);
-                atomicAdd((float*)(gbytes + o1), (float)acc1);
+                atomicAdd((float*)(gbytes + o0), (float)f0);
+                atomicAdd((float*)(gbytes + o1), (float)f1);
             }
         }
     };
@@ -663,7 +708,7 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
         Rec r;
         const int e = e0 + blk * WAVE + lane;
         r.xy = sxy[e];
-        r.row = sgrow[e] * 512;
+        r.row = sgrow[e] * (GZ ? 64 : 512);
         unsigned prev = __shfl_up(r.xy, 1, WAVE);
         if (lane == 0) prev = prev_last;
         const bool fresh = r.xy != prev;
@@ -674,11 +719,12 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     };
     constexpr int WALK_N = 8;      // entries per load-ahead group (2 groups in flight: 2*WALK_N VGPRs)
     const float2_t* const wlane = (const float2_t*)sw + hx;                    // + 2 * entry
+    const float* const wlane1 = (const float*)sw + (lane >> 4);                // GZ: the lane's own weight 2 hx + row, + 4 * entry
     // A row load is TWO instructions: v_readlane of the row's byte offset into an SGPR, and a buffer load that adds that SGPR
     // (soffset) and the lane's channel offset (voffset) to the descriptor's base - the global_load form needed a VALU add
     // per entry in between, and the walk is bound by instruction issue.
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)gcol, 0, (int)((unsigned)npts * 512u - (unsigned)(d * 64 + lvl * 32) * 4u), 0x00020000);
-    const int cvoff = c * 4;
+    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)gcol, 0, GZ ? (int)((unsigned)npts * 64u) : (int)((unsigned)npts * 512u - (unsigned)(d * 64 + lvl * 32) * 4u), 0x00020000);
+    const int cvoff = GZ ? (lane & 15) * 4 : c * 4;
 #define LOAD_HALF(buf, rec, half)                                                             \
     _Pragma("unroll") for (int t = 0; t < WALK_N; ++t) {                                      \
         const int rowb = __builtin_amdgcn_readlane((rec).row, (half) * WALK_N + t);           \
@@ -687,14 +733,16 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
 #define WALK_HALF(buf, rec, half, ebase)                                                      \
     _Pragma("unroll") for (int t = 0; t < WALK_N; ++t) {                                      \
         const int idx = (half) * WALK_N + t;                                                  \
-        const float2_t w2 = wlane[2 * ((ebase) + idx)];                                       \
+        float2_t w2 = {0.f, 0.f};                                                             \
+        if (GZ) w2[0] = wlane1[4 * ((ebase) + idx)];                                          \
+        else w2 = wlane[2 * ((ebase) + idx)];                                                 \
         if (((idx < 32 ? fresh_lo : fresh_hi) >> (idx & 31)) & 1u) {     /* one s_bitcmp on a 32-bit scalar */ \
             if (((idx < 32 ? adj_lo : adj_hi) >> (idx & 31)) & 1u) {                          \
                 /* next cell along the minor axis: its first texel column is our second one - keep those sums */ \
                 flush(true);                                                                  \
                 const acc_t s0 = __shfl_xor(acc0, 32, WAVE), s1 = __shfl_xor(acc1, 32, WAVE); \
                 acc0 = hx ? (acc_t)0 : s0;                                                    \
-                acc1 = hx ? (acc_t)0 : s1;                                                    \
+                acc1 = (hx || GZ) ? (acc_t)0 : s1;                                            \
                 if (DET) {            /* det_bad travels with the carried column's sums and with nothing else */ \
                     const int carried_bad = __shfl_xor((int)det_bad, 32, WAVE);               \
                     det_bad = !hx && carried_bad;                                             \
@@ -713,6 +761,8 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
             det_bad = det_bad || !(fabsf(t0_) < FIX_LIMIT) || !(fabsf(t1_) < FIX_LIMIT);      \
             acc0 += (acc_t)__float2ll_rn(t0_ * FIX_SCALE);                                    \
             acc1 += (acc_t)__float2ll_rn(t1_ * FIX_SCALE);                                    \
+        } else if (GZ) {                                                                      \
+            acc0 += (acc_t)(g * w2[0]);                                                       \
         } else {                                                                              \
             acc0 += (acc_t)(g * w2[0]);                                                       \
             acc1 += (acc_t)(g * w2[1]);                                                       \
@@ -825,7 +875,7 @@ bool eslam_scatter_can_reduce(bool render) {
 
 int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float* rays_o, const float* rays_d,
                      const float* z_or_pts, int64_t R, int S, bool render, const float* g_feat, const int* perm,
-                     hipStream_t st, const DecReduceArgs* red) {
+                     hipStream_t st, const DecReduceArgs* red, const eslam_decoders_t* gz_dec) {
     PlaneSet ps;
     for (int i = 0; i < NPL; ++i) {
         ps.p[i] = planes[i];
@@ -833,7 +883,19 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
     }
     const int64_t N = render ? R * S : R;
     const int nunits = render ? (int)R : (int)((N + 63) / 64);
-    // the walk addresses g_feat rows and plane texels with 32-bit byte offsets from a uniform base
+    // the walk addresses g_feat rows and plane texels with 32-bit byte offsets from a uniform base (rank-16 path: 64-byte
+    // rows from the decoder's half of gz[2][N][16], descriptor range N * 64 - inside the same limit, which the workspace's
+    // layout and the decoder backward's stores keep)
+    if (gz_dec && (!render || eslam_deterministic())) {
+        eslam_set_error("scatter: the rank-16 path serves the float render mode only");
+        return 1;
+    }
+    // gz[2][N][16]: the decoder backward's descriptor spans 2 N * 64 bytes, the walk's row offset goes up to N * 64 as an int
+    static_assert(2 * 64 <= 512 && ESLAM_HIDDEN * 4 == 64, "the rank-16 rows' offsets lie inside the N * 512 limit checked below");
+    if (gz_dec && (N * 128 >= ((int64_t)1 << 32) - 256 || N * 64 > INT32_MAX)) {
+        eslam_set_error("scatter: %lld points exceed the 32-bit offset range of the 16-wide gradient rows", (long long)N);
+        return 1;
+    }
     if (N * 512 >= ((int64_t)1 << 32)) {
         eslam_set_error("scatter: %lld points exceed the 32-bit offset range of the feature-gradient buffer (8.3 M): split "
                         "the batch", (long long)N);
@@ -871,7 +933,8 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
     }
 #define LAUNCH_SC(RD, PERM, SS, ...)                                                                                      \
     hipLaunchKernelGGL((scatter_sort_kernel<RD, false, ##__VA_ARGS__>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d, z_or_pts, \
-                       PERM, (int)R, SS, g_feat, bundle, nbundles, (long long*)nullptr, ShadowOff{}, red_args, red_blocks)
+                       PERM, (int)R, SS, g_feat, bundle, nbundles, (long long*)nullptr, ShadowOff{}, red_args, red_blocks, \
+                       gz_dec ? gz_dec->w1 : nullptr, gz_dec ? gz_dec->cw1 : nullptr)
     if (eslam_deterministic()) {
         // fixed-point scatter into the int64 shadow, then shadow -> float gradients (DET in the kernel's header comment)
         ShadowOff so;
@@ -921,11 +984,11 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
         }
         if (render)
             hipLaunchKernelGGL((scatter_sort_kernel<true, true>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d,
-                               z_or_pts, perm, (int)R, S, g_feat, bundle, nbundles, shadow, so, DecReduceArgs{}, 0);
+                               z_or_pts, perm, (int)R, S, g_feat, bundle, nbundles, shadow, so, DecReduceArgs{}, 0, nullptr, nullptr);
         else
             hipLaunchKernelGGL((scatter_sort_kernel<false, true>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d,
                                z_or_pts, (const int*)nullptr, (int)R, 64, g_feat, bundle, nbundles, shadow, so,
-                               DecReduceArgs{}, 0);
+                               DecReduceArgs{}, 0, nullptr, nullptr);
         if (int rc = eslam_check_launch("scatter_sort_kernel<det>")) return rc;
         for (int i = 0; i < NPL; ++i) {
             const int64_t numel = (int64_t)ESLAM_C_DIM * planes[i].h * planes[i].w;
@@ -934,7 +997,10 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
         }
         return eslam_check_launch("scatter_fixed_to_float_kernel");
     }
-    if (render) {
+    if (gz_dec) {
+        if (bm == 1024) LAUNCH_SC(true, perm, S, 2, true);
+        else LAUNCH_SC(true, perm, S, 4, true);
+    } else if (render) {
         if (bm == 1024) LAUNCH_SC(true, perm, S, 2);
         else LAUNCH_SC(true, perm, S);
     } else {
