@@ -445,6 +445,58 @@ int64_t eslam_depth_l1_workspace_bytes(int n_views);
 int eslam_depth_l1(const float* a, const float* b, int n_views, int64_t n_pixels, void* workspace, double* out,
                    eslam_stream_t stream);
 
+/* Render metrics and the frame visualiser's panel (reference src/utils/Frame_Visualizer.py:43-122): three operations on a
+ * rendered frame and its ground truth.  depth, gt_depth [H][W]; color, gt_color [H][W][3]; all float32 on the device.
+ * Every call launches on `stream` and never synchronises; bad arguments come back non-zero before any launch.
+ *
+ * eslam_frame_stats: out [4] (device, float64) =
+ *   n_valid        the number of pixels with gt_depth > 0
+ *   sum_abs_depth  the sum over those pixels of |depth - gt_depth|, the difference taken in float32 and widened to double
+ *   sum_sq_color   the sum over all 3 H W colour values of (color - gt_color)^2, unclipped: the difference taken in float32
+ *                  and squared in double (Slam.render_quality's mse before the division)
+ *   max_gt_depth   the largest gt_depth
+ * A two-stage fixed-order tree in float64 (no float atomics): a workgroup per ESLAM_STATS_BLOCK_PIXELS pixels, then one
+ * workgroup over the partials; bit-identical run to run.  workspace: eslam_frame_stats_workspace_bytes(H, W) bytes.
+ * 1 <= H, W <= 16384.                                                                                              */
+#define ESLAM_STATS_BLOCK_PIXELS 4096
+int64_t eslam_frame_stats_workspace_bytes(int H, int W);
+int eslam_frame_stats(const float* depth, const float* gt_depth, const float* color, const float* gt_color, int H, int W,
+                      void* workspace, double* out, eslam_stream_t stream);
+
+/* Mean SSIM (Wang, Bovik, Sheikh, Simoncelli 2004) of two [H][W][C] float32 images a and b, C = 1 or 3.  Inputs are clipped
+ * to [0, 1] on load (a NaN reads as 0).  The window is the 11 x 11 Gaussian with sigma = 1.5, w[k] = exp(-(k - 5)^2 / 4.5)
+ * normalised to sum 1 in float64 and rounded to float32, applied separably (rows, then columns) over the valid region only,
+ * no padding: the map is [H - 10][W - 10][C].  Population moments (no sample-covariance correction), C1 = 1e-4 and
+ * C2 = 9e-4 (data range 1).  H < 11 or W < 11 (or > 16384), or another C, is an argument error.
+ * One output tile of ESLAM_SSIM_TILE_H x ESLAM_SSIM_TILE_W pixels of one channel per workgroup: the tile and its 10-pixel
+ * halo of both images staged in LDS, the horizontal pass of the five moment images into LDS, the vertical pass and the
+ * formula in registers.  float32 variances are differences of nearly equal numbers, so the moments are taken of values
+ * shifted by a per-tile constant (variances and covariances do not depend on it).  Operation order, float32 and unfused,
+ * every window sum running k = 0 .. 10 as acc = w[0] v[0], then acc = acc + w[k] v[k]:
+ *   kx, ky = clip(a), clip(b) at the tile's first pixel (its top-left output position, same channel)
+ *   x = clip(a) - kx,  y = clip(b) - ky
+ *   h_x, h_y, h_xx, h_yy, h_xy = sum_k w[k] {x, y, x x, y y, x y}[r][j + k]
+ *   m_x, m_y, m_xx, m_yy, m_xy = sum_k w[k] h_*[i + k][j]
+ *   vx = m_xx - m_x m_x,  vy = m_yy - m_y m_y,  vxy = m_xy - m_x m_y,  ux = kx + m_x,  uy = ky + m_y
+ *   ssim = ((2 (ux uy) + C1) (2 vxy + C2)) / ((ux ux + uy uy + C1) (vx + vy + C2)), a true division
+ * map [H - 10][W - 10][C] float32 may be NULL.  mean [1] (device, float64) = the sum of the float32 map values by a
+ * fixed-order float64 tree (per tile, then over the tiles), divided by their number: bit-identical run to run.
+ * workspace: eslam_ssim_workspace_bytes(H, W, C) bytes (-1 for a shape eslam_ssim refuses).                          */
+#define ESLAM_SSIM_TILE_H 16
+#define ESLAM_SSIM_TILE_W 32
+int64_t eslam_ssim_workspace_bytes(int H, int W, int C);
+int eslam_ssim(const float* a, const float* b, int H, int W, int C, void* workspace, float* map, double* mean,
+               eslam_stream_t stream);
+
+/* out [2 H][3 W][3] uint8: the visualiser's 2 x 3 panel at the frame's own resolution.
+ * Row 0: gt_depth, depth, and |gt_depth - depth| forced to 0 where gt_depth == 0, each through the colour map:
+ *   vmax = float(stats[3]) read on the device (eslam_frame_stats' out), 1 when it is 0;  t = v / vmax, a true float32
+ *   division;  LUT index 0 for t <= 0 or NaN, otherwise min(255, int(t 256));  lut [256][3] uint8 on the device (plasma).
+ * Row 1: gt_color, color, and |gt_color - color| forced to 0 where gt_depth == 0, each clipped to [0, 1] (a NaN reads as
+ *   0), then uint8(c 255 + 0.5f): a float32 multiplication, then a float32 addition, truncated.                     */
+int eslam_vis_panel(const float* depth, const float* gt_depth, const float* color, const float* gt_color, int H, int W,
+                    const double* stats, const uint8_t* lut, uint8_t* out, eslam_stream_t stream);
+
 /* check_proj (src/tools/eval_recon.py:59-85) for a chunk of n_views candidate views: seen[k] (uint8, ORed into: set
  * to 1, never cleared) when any point of points [n_points,3] projects into view k.  w2c [n_views][12]: the 3x4 rows
  * (float32) of the float64 inverse, taken on the host, of c2w[k] with its columns 1 and 2 negated (eval_recon.py:64-68).

@@ -51,6 +51,9 @@ ICP_MOMENTS = 17             # eslam_icp_moments' out[]
 RASTER_LARGE_AREA = 64       # ESLAM_RASTER_LARGE_AREA
 RASTER_Z_NEAR = 0.01         # ESLAM_RASTER_Z_NEAR
 RASTER_Z_FAR = 20.0          # ESLAM_RASTER_Z_FAR
+STATS_BLOCK_PIXELS = 4096    # ESLAM_STATS_BLOCK_PIXELS: pixels per first-stage workgroup of eslam_frame_stats
+SSIM_TILE_H = 16             # ESLAM_SSIM_TILE_H, ESLAM_SSIM_TILE_W: output pixels per workgroup of eslam_ssim
+SSIM_TILE_W = 32
 Bound6 = ctypes.c_float * 6
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
@@ -121,6 +124,11 @@ SIGNATURES = {
     "eslam_depth_l1_workspace_bytes": (_i64, [_i]),
     "eslam_depth_l1": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "eslam_views_see_points": (_i, [_vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
+    "eslam_frame_stats_workspace_bytes": (_i64, [_i, _i]),
+    "eslam_frame_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "eslam_ssim_workspace_bytes": (_i64, [_i, _i, _i]),
+    "eslam_ssim": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "eslam_vis_panel": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "eslam_decode_bwd": (_i, [_PP, _DP, _BP, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_mapping_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_loss_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),

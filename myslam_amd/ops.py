@@ -1636,3 +1636,142 @@ def views_see_points(points, c2ws, K, H, W):
                                                          int(W), _hip.ptr(seen), _hip.stream_handle(dev)),
                        "eslam_views_see_points")
     return seen.bool()
+
+
+# ----------------------------------------------------------------------------------------------
+# render metrics and the frame visualiser's panel (reference src/utils/Frame_Visualizer.py; csrc/eslam_vis.hip)
+# ----------------------------------------------------------------------------------------------
+PLASMA_LUT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "plasma_lut.txt")
+
+
+def load_plasma_lut():
+    """The committed plasma table (data/plasma_lut.txt: 256 rows of R G B, CC0) as a numpy uint8 [256,3] array."""
+    import numpy as np
+    rows = np.loadtxt(PLASMA_LUT_PATH, dtype=np.int64, comments="#", ndmin=2)
+    if rows.shape != (256, 3) or rows.min() < 0 or rows.max() > 255:
+        raise RuntimeError(f"{PLASMA_LUT_PATH}: expected 256 rows of three values in [0, 255], got shape {rows.shape}")
+    return rows.astype(np.uint8)
+
+
+def plasma_lut(device):
+    """The committed plasma table on `device` as uint8 [256,3], uploaded once per device."""
+    def make():
+        return torch.from_numpy(load_plasma_lut()).to(device).contiguous()
+    return _cached(("plasma_lut", str(device)), make)
+
+
+def _frame_args(who, depth, color, gt_depth, gt_color):
+    """The four images of a rendered frame and its ground truth as contiguous float32 tensors on one GPU; `depth` may be the
+    float64 that render_img returns (cast with .float(), as Slam.render_quality does)."""
+    for name, t in (("depth", depth), ("color", color), ("gt_depth", gt_depth), ("gt_color", gt_color)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name}: expected a tensor on the GPU (got "
+                               f"{t.device if torch.is_tensor(t) else type(t).__name__}); the metrics and the panel have "
+                               "no CPU fallback")
+    if depth.dtype == torch.float64:
+        depth = depth.float()
+    for name, t in (("depth", depth), ("color", color), ("gt_depth", gt_depth), ("gt_color", gt_color)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name}: expected float32, got {t.dtype}")
+    dev = depth.device
+    if (depth.dim() != 2 or depth.shape[0] < 1 or depth.shape[1] < 1 or gt_depth.shape != depth.shape
+            or tuple(color.shape) != tuple(depth.shape) + (3,) or gt_color.shape != color.shape
+            or any(t.device != dev for t in (color, gt_depth, gt_color))):
+        raise RuntimeError(f"{who}: expected depth and gt_depth [H,W], color and gt_color [H,W,3] on one device, got "
+                           f"{tuple(depth.shape)}, {tuple(gt_depth.shape)}, {tuple(color.shape)}, {tuple(gt_color.shape)}")
+    return _c(depth.detach()), _c(color.detach()), _c(gt_depth.detach()), _c(gt_color.detach())
+
+
+def _frame_stats(depth, color, gt_depth, gt_color):
+    dev = depth.device
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    lib = _hip.lib()
+    nbytes = int(lib.eslam_frame_stats_workspace_bytes(H, W))
+    if nbytes < 0:
+        raise RuntimeError(f"frame_stats: image size {H} x {W} is out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(lib.eslam_frame_stats(_hip.ptr(depth), _hip.ptr(gt_depth), _hip.ptr(color), _hip.ptr(gt_color), H, W,
+                                         _hip.ptr(ws), _hip.ptr(out), _hip.stream_handle(dev)), "eslam_frame_stats")
+    return out
+
+
+def frame_stats(depth, color, gt_depth, gt_color):
+    """float64 [4] on the device: n_valid (pixels with gt_depth > 0), the sum over them of |depth - gt_depth|, the sum over all
+    colour values of (color - gt_color)^2, max gt_depth (eslam_frame_stats: a fixed-order float64 reduction).  On the caller's
+    current stream; no synchronisation."""
+    return _frame_stats(*_frame_args("frame_stats", depth, color, gt_depth, gt_color))
+
+
+def ssim(a, b, return_map=False):
+    """Mean SSIM of two float32 [H,W,C] (C = 1 or 3) or [H,W] images on the GPU, as a float64 scalar tensor on the device
+    (eslam_ssim: 11 x 11 Gaussian window, sigma 1.5, valid region, inputs clipped to [0, 1], C1 = 1e-4, C2 = 9e-4).  With
+    return_map also the float32 map [H-10,W-10,C] (or [H-10,W-10]).  On the caller's current stream; no synchronisation."""
+    _hip.require_gpu_f32("a", a)
+    _hip.require_gpu_f32("b", b)
+    if a.shape != b.shape or a.dim() not in (2, 3) or a.device != b.device:
+        raise RuntimeError(f"ssim: expected two [H,W,C] images of one shape on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    C = int(a.shape[2]) if a.dim() == 3 else 1
+    if H < 11 or W < 11 or C not in (1, 3):
+        raise RuntimeError(f"ssim: images of {H} x {W} x {C}: the 11 x 11 window needs H, W >= 11, and 1 or 3 channels")
+    a, b = _c(a.detach()), _c(b.detach())
+    dev = a.device
+    lib = _hip.lib()
+    nbytes = int(lib.eslam_ssim_workspace_bytes(H, W, C))
+    if nbytes < 0:
+        _hip.check(1, "eslam_ssim_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    mean = torch.empty(1, dtype=torch.float64, device=dev)
+    smap = torch.empty((H - 10, W - 10) + ((C,) if a.dim() == 3 else ()), dtype=torch.float32, device=dev) if return_map else None
+    with _hip.on_device(dev):
+        _hip.check(lib.eslam_ssim(_hip.ptr(a), _hip.ptr(b), H, W, C, _hip.ptr(ws), _hip.ptr(smap), _hip.ptr(mean),
+                                  _hip.stream_handle(dev)), "eslam_ssim")
+    return (mean[0], smap) if return_map else mean[0]
+
+
+def _vis_panel(depth, color, gt_depth, gt_color, stats):
+    dev = depth.device
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    lut = plasma_lut(dev)
+    out = torch.empty(2 * H, 3 * W, 3, dtype=torch.uint8, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_vis_panel(_hip.ptr(depth), _hip.ptr(gt_depth), _hip.ptr(color), _hip.ptr(gt_color), H, W,
+                                              _hip.ptr(stats), _hip.ptr(lut), _hip.ptr(out), _hip.stream_handle(dev)),
+                   "eslam_vis_panel")
+    return out
+
+
+def vis_panel(depth, color, gt_depth, gt_color, stats=None):
+    """uint8 [2H,3W,3] on the device: the frame visualiser's panel (eslam_vis_panel).  Row 0: input depth, rendered depth,
+    depth residual through the plasma map with vmax = max gt_depth; row 1: input colour, rendered colour, colour residual;
+    residuals are 0 where gt_depth == 0.  `stats` is frame_stats' result for the same frame, computed here when not given.
+    On the caller's current stream; no synchronisation."""
+    depth, color, gt_depth, gt_color = _frame_args("vis_panel", depth, color, gt_depth, gt_color)
+    if stats is None:
+        stats = _frame_stats(depth, color, gt_depth, gt_color)
+    elif (not torch.is_tensor(stats) or stats.device != depth.device or stats.dtype != torch.float64 or tuple(stats.shape) != (4,)
+          or not stats.is_contiguous()):
+        raise RuntimeError("vis_panel: stats must be frame_stats' float64 [4] tensor on the images' device")
+    return _vis_panel(depth, color, gt_depth, gt_color, stats)
+
+
+def _metrics_from(stats_ssim, n_color_values):
+    """dict(psnr, ssim, depth_l1, n_valid) from the five numbers [n_valid, sum |d|, sum c^2, max, ssim] on the host."""
+    n_valid, s_abs, s_sq, _, ss = (float(v) for v in stats_ssim)
+    mse = s_sq / n_color_values
+    psnr = -10.0 * math.log10(mse) if mse > 0.0 else float("inf")
+    return dict(psnr=psnr, ssim=ss, depth_l1=s_abs / n_valid if n_valid > 0 else float("nan"), n_valid=n_valid)
+
+
+def frame_metrics(depth, color, gt_depth, gt_color, stats=None):
+    """dict(psnr, ssim, depth_l1, n_valid) of Python floats for a rendered frame against its ground truth:
+    psnr = -10 log10(sum_sq_color / (3 H W)), ssim = ssim(color, gt_color), depth_l1 = sum_abs_depth / n_valid (nan when no
+    pixel has depth).  The one call here that synchronises (one download of five numbers).  `stats`: frame_stats' result
+    for the same frame when the caller already has it."""
+    depth, color, gt_depth, gt_color = _frame_args("frame_metrics", depth, color, gt_depth, gt_color)
+    if stats is None:
+        stats = _frame_stats(depth, color, gt_depth, gt_color)
+    s = ssim(color, gt_color)
+    return _metrics_from(torch.cat([stats, s[None]]).cpu().tolist(), 3 * depth.shape[0] * depth.shape[1])

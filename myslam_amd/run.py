@@ -1,10 +1,12 @@
 """Run the system on a dataset from its YAML config, as the reference's run.py does:
 
-    python -m myslam_amd.run configs/Replica/room0.yaml [--input_folder D] [--output D] [--graph]
+    python -m myslam_amd.run configs/Replica/room0.yaml [--input_folder D] [--output D] [--graph] [--render_eval N]
 
 The config is read over the file its `inherit_from` names and over the defaults file: configs/ESLAM.yaml from the
 working directory, as the reference has it, else the nearest ESLAM.yaml in a directory above the config.  --graph replays
-every optimisation iteration as a captured hipGraph (slam_graph.GraphedSlam)."""
+every optimisation iteration as a captured hipGraph (slam_graph.GraphedSlam).  --render_eval N sets the config's
+render_eval.every: after the run every N-th frame is rendered at its estimated pose and PSNR, SSIM and depth L1 are written
+to <output>/render_eval.json."""
 import argparse
 import os
 
@@ -35,8 +37,12 @@ def main(argv=None):
     parser.add_argument('--output', type=str,
                         help='output folder, this have higher priority, can overwrite the one in config file')
     parser.add_argument('--graph', action='store_true', help='replay the iterations as captured hipGraphs')
+    parser.add_argument('--render_eval', type=int, metavar='N',
+                        help='render every N-th frame at its estimated pose after the run; PSNR, SSIM, depth L1 to render_eval.json')
     args = parser.parse_args(argv)
     cfg = config.load_config(args.config, default_config_for(args.config))
+    if args.render_eval is not None:
+        cfg['render_eval'] = dict(every=args.render_eval)
     eslam = ESLAM(cfg, args)
     eslam.run()
     return eslam

@@ -153,6 +153,11 @@ class Slam:
         self.keyframe_list = []
         self.keyframe_dict = []
         self.stats = dict(tracking_iters=0, mapping_iters=0, tracking_rays=0, mapping_rays=0)
+        # on_iter(stage, idx, it, gt_depth, gt_color, pose), when set, is called at the head of every optimisation iteration:
+        # stage "tracking" with that iteration's [1,7] pose (Tracker.py:300-302), "mapping" with the c2w the mapper was given
+        # (Mapper.py:308-310); frame 0, which is not tracked, gives one "tracking" call with it = 0 and the ground-truth c2w
+        # (Tracker.py:276-279).  The driver hangs the frame visualisers on it (src/ESLAM.py).
+        self.on_iter = None
 
     # ------------------------------------------------------------------------------------------------------------
     def _precision(self):
@@ -184,8 +189,10 @@ class Slam:
         for p in self.decoders.parameters():
             p.requires_grad_(False)                                                   # Tracker.py:111-112
         best, best_pose = float("inf"), None
-        for _ in range(cfg.tracking_iters):
+        for it in range(cfg.tracking_iters):
             pose = torch.cat([R, T], -1)
+            if self.on_iter is not None:
+                self.on_iter("tracking", idx, it, gt_depth, gt_color, pose)
             c2w = be.cam_pose_to_matrix(pose)
             ro, rd, gd, gc = be.get_samples(cfg.ignore_edge_H, sc.H - cfg.ignore_edge_H, cfg.ignore_edge_W,
                                             sc.W - cfg.ignore_edge_W, cfg.tracking_pixels, sc.H, sc.W, sc.fx, sc.fy,
@@ -244,7 +251,9 @@ class Slam:
             cam_poses = torch.nn.Parameter(be.matrix_to_cam_pose(c2ws[1:]))
             groups.append({"params": [cam_poses], "lr": cfg.joint_opt_cam_lr})
         opt = be.Adam(groups)
-        for _ in range(iters):
+        for it in range(iters):
+            if self.on_iter is not None:
+                self.on_iter("mapping", idx, it, gt_depth, gt_color, cur_c2w)
             c2ws_ = torch.cat([c2ws[0:1], be.cam_pose_to_matrix(cam_poses)], 0) if joint else c2ws
             ro, rd, gd, gc = be.get_samples(0, sc.H, 0, sc.W, pixs, sc.H, sc.W, sc.fx, sc.fy, sc.cx, sc.cy, c2ws_, gds,
                                             gcs, self.device)
@@ -276,6 +285,8 @@ class Slam:
         for idx, gt_color, gt_depth, gt_c2w in frames:
             if idx == 0:
                 c2w = gt_c2w.clone()                                                   # Tracker.py:263-264
+                if self.on_iter is not None:                                           # Tracker.py:276-279
+                    self.on_iter("tracking", 0, 0, gt_depth, gt_color, c2w)
             else:
                 c2w = self.track(idx, gt_color, gt_depth)
             self.estimate_c2w_list.append(c2w.detach().clone())
@@ -301,3 +312,11 @@ class Slam:
         l1 = float((depth.float() - gt_depth)[valid].abs().mean())
         mse = float(((color - gt_color) ** 2).mean())
         return dict(psnr=float(-10.0 * torch.log10(torch.tensor(mse))), depth_l1=l1)
+
+    def render_report(self, gt_color, gt_depth, c2w):
+        """dict(psnr, ssim, depth_l1, n_valid) of one frame rendered from c2w against its ground truth (ops.frame_metrics: the
+        sums, the SSIM and nothing else leave the device).  What a sequence's render evaluation reports per frame."""
+        from . import ops
+        with torch.no_grad(), self._precision():      # the field that is evaluated is the one that was trained
+            depth, color = self.be.render_img(self.all_planes, self.decoders, c2w, self.truncation, gt_depth)
+        return ops.frame_metrics(depth, color, gt_depth, gt_color)

@@ -151,7 +151,9 @@ class GraphedSlam(Slam):
         st.color[0].copy_(gt_color)
         st.init.copy_(cam_pose)
         st.reset()
-        for _ in range(cfg.tracking_iters):
+        for it in range(cfg.tracking_iters):
+            if self.on_iter is not None:                                              # Tracker.py:300-302, between the replays
+                self.on_iter("tracking", idx, it, gt_depth, gt_color, torch.cat([st.R, st.T], -1).detach())
             st.graph.replay()
         self.stats["tracking_iters"] += cfg.tracking_iters
         self.stats["tracking_rays"] += cfg.tracking_iters * cfg.tracking_pixels
@@ -238,7 +240,9 @@ class GraphedSlam(Slam):
         if joint:
             st.cam_init.copy_(be.matrix_to_cam_pose(c2ws[1:]))
         st.reset()
-        for _ in range(iters):
+        for it in range(iters):
+            if self.on_iter is not None:                                              # Mapper.py:308-310
+                self.on_iter("mapping", idx, it, gt_depth, gt_color, cur_c2w)
             st.graph.replay()
         self.stats["mapping_iters"] += iters
         self.stats["mapping_rays"] += iters * st.rays

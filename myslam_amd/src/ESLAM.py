@@ -9,7 +9,8 @@ camera after update_cam, the bound, the frame reader, the mesher.  What differs 
 and maps in the lock-step order the reference's two processes synchronise to (slam.Slam, or slam_graph.GraphedSlam with
 args.graph), fed by datasets.FrameStream, which prepares the frames on the device.  Slam.run's schedule is kept as it is:
 unlike the reference's mapper, the last frame is not mapped unless the schedule maps it, and frame n_img - 2 is not
-added as a keyframe.  The visualisers are not built.
+added as a keyframe.  The in-loop frame visualisers (utils/Frame_Visualizer.py) hang on the loop's
+on_iter hook when the config has tracking.vis_freq / mapping.vis_freq; the offline viewer (visualizer.py) is not built.
 
 Written under <output>/:
     ckpts/NNNNN.tar            checkpoint.save, every mapping.ckpt_freq frames (mapped frames only, as the reference's
@@ -18,6 +19,12 @@ Written under <output>/:
                                skipped with mapping.no_mesh_on_first_frame
     mesh/final_mesh.ply        (final_mesh_eval_rec.ply with meshing.eval_rec) and its culled copy, at the end
     ate.json                   eval_ate.evaluate of the estimated against the dataset's trajectory
+    tracking_vis/NNNNN_IIII.jpg, mapping_vis/NNNNN_IIII.jpg
+                               the visualisers' panels: frame NNNNN, iteration IIII, every vis_freq frames and
+                               vis_inside_freq iterations; frame 0 skipped with no_vis_on_first_frame (Tracker.py:276-302,
+                               Mapper.py:308-310)
+    render_eval.json           with the top-level key render_eval: {every: N} (ours, like mixed_precision; absent or 0 = off):
+                               PSNR, SSIM and depth L1 of every N-th frame rendered at its estimated pose, and their means
 """
 import json
 import os
@@ -29,6 +36,7 @@ from ..scene import scene_from_config
 from ..slam import Slam, SlamConfig
 from .tools.cull_mesh import cull_mesh
 from .utils.datasets import FrameStream, get_dataset
+from .utils.Frame_Visualizer import Frame_Visualizer
 from .utils.Mesher import Mesher
 
 
@@ -64,6 +72,9 @@ class ESLAM:
         self.no_log_on_first_frame = bool(m.get('no_log_on_first_frame', False))
         self.no_mesh_on_first_frame = bool(m.get('no_mesh_on_first_frame', False))
         self.eval_rec = bool(cfg['meshing']['eval_rec'])
+        self.render_eval_every = int((cfg.get('render_eval') or {}).get('every', 0) or 0)
+        self.render_eval = None
+        self.visualizers = {}
         self.slam = None
         self.stats = None
         self.ate = None
@@ -101,6 +112,47 @@ class ESLAM:
         if idx % self.mesh_freq == 0 and not (idx == 0 and self.no_mesh_on_first_frame):
             self._mesh(s, os.path.join(self.output, 'mesh', f'{idx:05d}_mesh.ply'), idx + 1)
 
+    def _install_visualizers(self, s):
+        """A Frame_Visualizer per stage whose section has vis_freq and vis_inside_freq (a missing key = off, as in a config
+        written before them), and the on_iter hook that dispatches to them.  The hook is left unset when no call could pass
+        a gate: frame 0 is the only multiple of a vis_freq >= n_img, and no_vis_on_first_frame skips it."""
+        fires = False
+        for stage in ('tracking', 'mapping'):
+            sec = self.cfg[stage]
+            freq, inside = sec.get('vis_freq'), sec.get('vis_inside_freq')
+            if freq is None or inside is None or int(freq) <= 0 or int(inside) <= 0:
+                continue
+            vis = Frame_Visualizer(freq=int(freq), inside_freq=int(inside), vis_dir=os.path.join(self.output, f'{stage}_vis'),
+                                   renderer=s.be.renderer, truncation=self.truncation, verbose=self.verbose, device=self.device)
+            skip_first = bool(sec.get('no_vis_on_first_frame', False))
+            self.visualizers[stage] = (vis, skip_first)
+            fires = fires or not (skip_first and int(freq) >= self.n_img)
+        if not fires:
+            return
+
+        def on_iter(stage, idx, it, gt_depth, gt_color, pose):
+            entry = self.visualizers.get(stage)
+            if entry is None or (idx == 0 and entry[1]):
+                return
+            with s._precision():
+                entry[0].save_imgs(idx, it, gt_depth, gt_color, pose, s.all_planes, s.decoders)
+        s.on_iter = on_iter
+
+    def _render_eval(self, s):
+        """render_eval.json: every N-th frame of the sequence, read again, rendered at its estimated pose."""
+        rows = []
+        for idx, gt_color, gt_depth, _ in FrameStream(self.frame_reader, self.device, prefetch=2):
+            if idx % self.render_eval_every != 0 or idx >= len(s.estimate_c2w_list):
+                continue
+            r = s.render_report(gt_color, gt_depth, s.estimate_c2w_list[idx])
+            rows.append(dict(idx=int(idx), psnr=r['psnr'], ssim=r['ssim'], depth_l1=r['depth_l1'] / self.scale))
+        n = max(len(rows), 1)
+        self.render_eval = dict(every=self.render_eval_every, frames=rows,
+                                **{k: sum(r[k] for r in rows) / n for k in ('psnr', 'ssim', 'depth_l1')})
+        with open(os.path.join(self.output, 'render_eval.json'), 'w') as f:
+            json.dump(self.render_eval, f, indent=1)
+            f.write('\n')
+
     def run(self):
         """Track and map the whole sequence; returns the loop's stats."""
         if self.n_img == 0:
@@ -113,11 +165,14 @@ class ESLAM:
         else:
             s = Slam(self.scene, self.slam_config, device=self.device, seed=seed)
         self.slam = s
+        self._install_visualizers(s)
         frames = FrameStream(self.frame_reader, self.device, prefetch=2)
         s.run(frames, on_frame=self._on_frame)
 
         name = 'final_mesh_eval_rec.ply' if self.eval_rec else 'final_mesh.ply'
         self._mesh(s, os.path.join(self.output, 'mesh', name), self.n_img)            # Mapper.py:448-455
+        if self.render_eval_every > 0:
+            self._render_eval(s)
 
         est = [c.cpu().numpy() for c in s.estimate_c2w_list]
         gt = [c.cpu().numpy() for c in s.gt_c2w_list]
@@ -129,4 +184,8 @@ class ESLAM:
             f.write('\n')
         self.stats = s.stats
         print(f"ATE rmse {self.ate['rmse'] * 100:.2f} cm over {len(est)} frames; {s.stats}")
+        if self.render_eval is not None:
+            q = self.render_eval
+            print(f"Render: PSNR {q['psnr']:.2f} dB, SSIM {q['ssim']:.4f}, depth L1 {q['depth_l1'] * 100:.2f} cm over "
+                  f"{len(q['frames'])} frames (every {q['every']})")
         return self.stats
