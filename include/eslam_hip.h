@@ -445,6 +445,45 @@ int64_t eslam_depth_l1_workspace_bytes(int n_views);
 int eslam_depth_l1(const float* a, const float* b, int n_views, int64_t n_pixels, void* workspace, double* out,
                    eslam_stream_t stream);
 
+/* The offline viewer's headless colour renderer (reference src/tools/visualizer_util.py:178-200: the open3d window with
+ * point_size = 4 and mesh_show_back_face = False, showing an unlit mesh and point clouds).  All geometry of a chunk of
+ * views composes through one buffer of uint64 keys [n_views][H][W] at the start of `workspace`: the high word is the bits
+ * of the camera-space depth z (a positive float orders as its bits), the low word the pixel's RGBA8, R in the lowest byte.
+ *   eslam_viewer_begin    clears the keys to all ones;
+ *   eslam_viewer_mesh     every fragment does a 64-bit atomicMin into its pixel's key;  (visualizer_util.py:110-115)
+ *   eslam_viewer_points   the same for points drawn size x size pixels;                 (visualizer_util.py:57-59, 131-148, 182)
+ *   eslam_viewer_resolve  keys -> image [n_views][H][W][3] uint8 and, when depth is not NULL, depth [n_views][H][W]
+ *                         float32; untouched pixels get the background colour and depth 0.  (capture_screen_image, :175)
+ * Any number of mesh and point calls may fall between begin and resolve, all with the begin's n_views, H, W and workspace.
+ * The nearest fragment wins and equal depths go to the smaller colour word, so the image depends neither on the order of
+ * the calls nor on the order of execution: bit-identical run to run.
+ * Mesh fragments: setup, skipped triangles, pixel box, near-plane rule, edge functions E_k and depth z are those of
+ * eslam_raster_depth above (with return of the depth and no culling: the same bits), and so are large_area, the two triangle
+ * paths and the queue.  Colour: barycentrics b_k = E_k / ((E_0 + E_1) + E_2) (perspective-correct: E_0 = b_0 det[v0 v1 v2] / z;
+ * b = (1, 0, 0) should the sum be 0), per channel c = (b_0 c_0 + b_1 c_1) + b_2 c_2 with c_k the vertex's uint8 as float,
+ * clamped to [0, 255], stored as (uint8)floor(c + 0.5); alpha 255.  colors [n_verts][4] uint8 (the PLY's layout, 4-byte
+ * aligned, the fourth byte ignored) or NULL = every vertex (200, 200, 200).  cull_backfaces != 0: a triangle with
+ * (n . v0) >= 0, n = (v1 - v0) x (v2 - v0) in the camera frame (its normal points away from the camera), emits nothing.
+ * Point fragments, float32 operation by operation: c = w2c [p, 1], each row ((m0 x + m1 y) + m2 z) + m3; skipped unless
+ * z_near <= c.z <= z_far; u = fx c.x / c.z + cx, v = fy c.y / c.z + cy; x0 = (int)ceil(clamp(u - size / 2, -size, W)),
+ * y0 = (int)ceil(clamp(v - size / 2, -size, H)) (fmax first: NaN becomes -size); the point covers the pixels
+ * x0 .. x0 + size - 1, y0 .. y0 + size - 1 inside the image, each with the key of c.z and the point's colour, alpha 255.
+ * rgba: [n_points][4] uint8 when per_point != 0, else one [4] for the call.  1 <= size <= ESLAM_VIEWER_MAX_POINT_SIZE.
+ * workspace: eslam_viewer_workspace_bytes(n_faces, n_views, H, W) bytes for meshes of at most n_faces faces (keys, tile
+ * counters, tile queues).  H, W <= 16384.  Zero views, faces or points are valid and launch nothing.  Every call launches on
+ * `stream` and never synchronises; bad arguments come back non-zero, with eslam_last_error() set, before any launch.      */
+#define ESLAM_VIEWER_MAX_POINT_SIZE 16
+int64_t eslam_viewer_workspace_bytes(int64_t n_faces, int n_views, int H, int W);
+int eslam_viewer_begin(int n_views, int H, int W, void* workspace, eslam_stream_t stream);
+int eslam_viewer_mesh(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const uint8_t* colors,
+                      const float* w2c, int n_views, float fx, float fy, float cx, float cy, int H, int W, float z_near,
+                      float z_far, int cull_backfaces, int large_area, void* workspace, eslam_stream_t stream);
+int eslam_viewer_points(const float* points, int64_t n_points, const uint8_t* rgba, int per_point, int size, const float* w2c,
+                        int n_views, float fx, float fy, float cx, float cy, int H, int W, float z_near, float z_far,
+                        void* workspace, eslam_stream_t stream);
+int eslam_viewer_resolve(int n_views, int H, int W, int bg_r, int bg_g, int bg_b, const void* workspace, uint8_t* image,
+                         float* depth, eslam_stream_t stream);
+
 /* Render metrics and the frame visualiser's panel (reference src/utils/Frame_Visualizer.py:43-122): three operations on a
  * rendered frame and its ground truth.  depth, gt_depth [H][W]; color, gt_color [H][W][3]; all float32 on the device.
  * Every call launches on `stream` and never synchronises; bad arguments come back non-zero before any launch.

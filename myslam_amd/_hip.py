@@ -121,6 +121,11 @@ SIGNATURES = {
     "eslam_icp_moments": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "eslam_raster_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
     "eslam_raster_depth": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
+    "eslam_viewer_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "eslam_viewer_begin": (_i, [_i, _i, _i, _vp, _vp]),
+    "eslam_viewer_mesh": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _i, _i, _vp, _vp]),
+    "eslam_viewer_points": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _vp, _vp]),
+    "eslam_viewer_resolve": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "eslam_depth_l1_workspace_bytes": (_i64, [_i]),
     "eslam_depth_l1": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "eslam_views_see_points": (_i, [_vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),

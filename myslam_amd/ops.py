@@ -1598,6 +1598,87 @@ def render_mesh_depth(verts, faces, c2ws, K, H, W, z_near=_hip.RASTER_Z_NEAR, z_
     return out
 
 
+def _u8_rows(name, t, dev, n=None):
+    """uint8 [n,4] on dev (alpha 255) from a [n,3] / [n,4] colour tensor, or [1,4] from a [3] / [4] one."""
+    c = torch.as_tensor(t)
+    if c.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: expected uint8 colours, got {c.dtype}")
+    c = c.detach().to(dev)
+    if c.dim() == 1:
+        c = c[None]
+    if c.dim() != 2 or c.shape[1] not in (3, 4) or (n is not None and c.shape[0] not in (1, n)):
+        raise RuntimeError(f"{name}: expected [3|4] or [{n},3|4] colours, got {tuple(c.shape)}")
+    out = torch.full((c.shape[0], 4), 255, dtype=torch.uint8, device=dev)
+    out[:, :3] = c[:, :3]
+    return out
+
+
+def render_view(meshes, points, c2ws, K, H, W, background=(255, 255, 255), z_near=_hip.RASTER_Z_NEAR, z_far=_hip.RASTER_Z_FAR,
+                cull_backfaces=True, chunk=8, large_area=0, return_depth=False):
+    """uint8 [n,H,W,3] on the GPU: the colour images of meshes and point clouds from the cameras c2ws [n,4,4] (the
+    convention of render_mesh_depth: the camera looks along +z, y down), K = (fx, fy, cx, cy); what the reference's open3d
+    window shows (visualizer_util.py:178-200): meshes unlit with their vertex colours, back faces hidden when
+    cull_backfaces, points drawn size x size pixels, the nearest fragment at each pixel (eslam_viewer_*).
+    meshes: a list of (verts float32 [V,3], faces [F,3], colors uint8 [V,3|4] or None = grey); points: a list of
+    (xyz float32 [N,3], rgb uint8 [3|4] for all or [N,3|4], size in pixels).  All tensors on one GPU.  Views are rendered `chunk` at a
+    time; the poses are inverted on the host in float64.  With return_depth also float32 [n,H,W]: the camera-space z of the
+    winning fragment, 0 where the background shows.  The images depend neither on the order of the lists nor on large_area."""
+    ms, ps, dev = [], [], None
+    for k, (verts, faces, colors) in enumerate(meshes):
+        v = torch.as_tensor(verts)
+        _hip.require_gpu_f32(f"meshes[{k}] verts", v)
+        dev = v.device if dev is None else dev
+        v = _c(v.detach().reshape(-1, 3))
+        f = torch.as_tensor(faces)
+        if not f.is_cuda:
+            raise RuntimeError(f"meshes[{k}] faces: expected a tensor on the GPU (got device {f.device}); the renderer has no CPU fallback")
+        f = _c(f.detach().to(dev, torch.int32).reshape(-1, 3))
+        c = None
+        if colors is not None:
+            if not torch.as_tensor(colors).is_cuda:
+                raise RuntimeError(f"meshes[{k}] colors: expected a tensor on the GPU; the renderer has no CPU fallback")
+            c = _u8_rows(f"meshes[{k}] colors", colors, dev, v.shape[0])
+            if c.shape[0] != v.shape[0]:
+                raise RuntimeError(f"meshes[{k}] colors: expected one colour per vertex ({v.shape[0]}), got {c.shape[0]}")
+        ms.append((v, f, c))
+    for k, (xyz, rgb, size) in enumerate(points):
+        p = torch.as_tensor(xyz)
+        _hip.require_gpu_f32(f"points[{k}] xyz", p)
+        dev = p.device if dev is None else dev
+        p = _c(p.detach().reshape(-1, 3))
+        ps.append((p, _u8_rows(f"points[{k}] rgb", rgb, dev, p.shape[0]), int(size)))
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    fx, fy, cx, cy = (float(k) for k in K)
+    H, W, chunk = int(H), int(W), max(1, int(chunk))
+    bg = [int(b) for b in background]
+    w2c = _w2c_rows(c2ws, dev)
+    n = w2c.shape[0]
+    out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+    depth = torch.empty(n, H, W, dtype=torch.float32, device=dev) if return_depth else None
+    lib = _hip.lib()
+    n_faces = max([m[1].shape[0] for m in ms], default=0)
+    nb = int(lib.eslam_viewer_workspace_bytes(n_faces, max(1, min(chunk, n)), H, W))
+    if nb < 0:
+        raise RuntimeError(f"render_view: bad sizes ({n_faces} faces, image {W} x {H})")
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    st = _hip.stream_handle(dev)
+    with _hip.on_device(dev):
+        for lo in range(0, n, chunk):
+            k = min(chunk, n - lo)
+            cam = (_hip.ptr(w2c[lo:]), k, fx, fy, cx, cy, H, W, float(z_near), float(z_far))
+            _hip.check(lib.eslam_viewer_begin(k, H, W, _hip.ptr(ws), st), "eslam_viewer_begin")
+            for v, f, c in ms:
+                _hip.check(lib.eslam_viewer_mesh(_hip.ptr(v), v.shape[0], _hip.ptr(f), f.shape[0], _hip.ptr(c) if c is not None else None,
+                                                 *cam, int(bool(cull_backfaces)), int(large_area), _hip.ptr(ws), st), "eslam_viewer_mesh")
+            for p, c, size in ps:
+                _hip.check(lib.eslam_viewer_points(_hip.ptr(p), p.shape[0], _hip.ptr(c), int(c.shape[0] != 1), size,
+                                                   *cam, _hip.ptr(ws), st), "eslam_viewer_points")
+            _hip.check(lib.eslam_viewer_resolve(k, H, W, bg[0], bg[1], bg[2], _hip.ptr(ws), _hip.ptr(out[lo:]),
+                                                _hip.ptr(depth[lo:]) if return_depth else None, st), "eslam_viewer_resolve")
+    return (out, depth) if return_depth else out
+
+
 def depth_l1(a, b):
     """float64 [n] on the device: per view the sum over the pixels of |a - b|, a and b float32 [n,H,W] (eslam_depth_l1:
     a fixed-order float64 reduction)."""
