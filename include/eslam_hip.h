@@ -400,6 +400,30 @@ int64_t eslam_icp_moments_workspace_bytes(void);
 int eslam_icp_moments(const float* src, const float* tgt, const float* dist, const int32_t* idx, int64_t n,
                       float threshold, void* workspace, double* out, eslam_stream_t stream);
 
+/* Mesh clean-up (src/tools/clean_mesh.py): the vertex merge of trimesh's process() that closes the reference's
+ * src/tools/cull_mesh.py:109, and the connected components behind NICE-SLAM's remove_small_geometry.  verts [n_verts,3]
+ * float32, faces [n_faces,3] int32 with every index in [0, n_verts) (the caller checks: the kernels do not).  Counts are
+ * 0 .. ESLAM_MESH_MAX_COUNT; a count outside comes back non-zero before any launch, zero vertices return 0 without one.
+ * Every result is a function of the input alone (a smallest index, an exact integer sum): bit-identical run to run.
+ *
+ * eslam_mesh_weld: rep [n_verts] int32 = the smallest index u whose position equals v's, coordinate by coordinate as
+ *   floats with -0 == +0 (bit patterns compared after -0 is turned into +0: one ulp apart is different, denormals are
+ *   ordinary values); a vertex with a NaN or infinite coordinate gets -1 and takes no part.
+ *   workspace: eslam_mesh_weld_workspace_bytes(n_verts) bytes, any contents: an open-addressing table of int32 vertex
+ *   indices with S slots, S the power of two >= 2 n_verts and >= ESLAM_MESH_WELD_MIN_SLOTS; 4 S bytes (-1 for a bad count).
+ * eslam_mesh_components: label [n_verts] int32 = the smallest vertex index of v's component, where two vertices are
+ *   connected when a chain of faces that share a VERTEX joins them (trimesh splits by shared EDGES: two pieces touching at
+ *   one vertex are one component here).  A vertex in no face labels itself; a face may repeat an index.
+ * eslam_mesh_component_sizes: face_count [n_verts] int32, cleared by the call, then face_count[label[faces[f][0]]] += 1
+ *   for every face: the face count of a component at its label, 0 elsewhere.  Integer atomics: exact.                 */
+#define ESLAM_MESH_MAX_COUNT (1 << 30)
+#define ESLAM_MESH_WELD_MIN_SLOTS 64
+int64_t eslam_mesh_weld_workspace_bytes(int64_t n_verts);
+int eslam_mesh_weld(const float* verts, int64_t n_verts, void* workspace, int32_t* rep, eslam_stream_t stream);
+int eslam_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* label, eslam_stream_t stream);
+int eslam_mesh_component_sizes(const int32_t* faces, int64_t n_faces, const int32_t* label, int64_t n_verts,
+                               int32_t* face_count, eslam_stream_t stream);
+
 /* Depth images of a triangle mesh for a chunk of n_views views in one call: replaces open3d's visualiser in
  * src/tools/eval_recon.py:177-201 (capture_depth_float_buffer(True) with mesh_show_back_face and set_constant_z_far(20)).
  * verts [n_verts,3] float32, faces [n_faces,3] int32, w2c [n_views][12] the 3x4 rows (float32, inverted from c2w on the

@@ -48,6 +48,7 @@ NN_MAX_CELLS = 1 << 24       # ESLAM_NN_MAX_CELLS
 NN_CELLS_PER_POINT = 2       # ESLAM_NN_CELLS_PER_POINT
 NN_INPUT_ORDER = 1           # ESLAM_NN_INPUT_ORDER
 ICP_MOMENTS = 17             # eslam_icp_moments' out[]
+MESH_MAX_COUNT = 1 << 30     # ESLAM_MESH_MAX_COUNT: vertices / faces of the mesh clean-up entry points
 RASTER_LARGE_AREA = 64       # ESLAM_RASTER_LARGE_AREA
 RASTER_Z_NEAR = 0.01         # ESLAM_RASTER_Z_NEAR
 RASTER_Z_FAR = 20.0          # ESLAM_RASTER_Z_FAR
@@ -119,6 +120,10 @@ SIGNATURES = {
     "eslam_nn_query": (_i, [_GP, _vp, _i64, _vp, _i64, _f, _i, _vp, _vp, _vp, _vp]),
     "eslam_icp_moments_workspace_bytes": (_i64, []),
     "eslam_icp_moments": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
+    "eslam_mesh_weld_workspace_bytes": (_i64, [_i64]),
+    "eslam_mesh_weld": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "eslam_mesh_components": (_i, [_vp, _i64, _i64, _vp, _vp]),
+    "eslam_mesh_component_sizes": (_i, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "eslam_raster_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
     "eslam_raster_depth": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
     "eslam_viewer_workspace_bytes": (_i64, [_i64, _i, _i, _i]),

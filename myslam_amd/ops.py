@@ -1525,6 +1525,94 @@ def icp_moments(src, tgt, dist, idx, threshold):
     return out
 
 
+# mesh clean-up (src/tools/clean_mesh.py): vertex merge, connected components, their face counts
+def _mesh_gpu(name, t, dtype, cols):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a tensor on the GPU (got {getattr(t, 'device', type(t).__name__)}); the mesh "
+                           "clean-up has no CPU fallback")
+    t = t.detach()
+    if cols:
+        t = t.reshape(-1, cols)
+    else:
+        t = t.reshape(-1)
+    n = t.shape[0]
+    if n > _hip.MESH_MAX_COUNT:
+        raise RuntimeError(f"{name}: {n} entries, at most 2^30")
+    return _c(t.to(dtype))
+
+
+def _mesh_faces(faces, n_verts):
+    """int32 [F,3] on the GPU, every index checked once against [0, n_verts) (one sync): the kernels do not check."""
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError(f"faces: expected a tensor on the GPU (got {getattr(faces, 'device', type(faces).__name__)})")
+    f = faces.detach().reshape(-1, 3)
+    if f.shape[0] > _hip.MESH_MAX_COUNT:
+        raise RuntimeError(f"faces: {f.shape[0]} faces, at most 2^30")
+    if f.shape[0]:
+        lo, hi = f.aminmax()
+        lo, hi = int(lo), int(hi)
+        if lo < 0 or hi >= n_verts:
+            raise ValueError(f"faces: indices span [{lo}, {hi}], the mesh has {n_verts} vertices")
+    return _c(f.to(torch.int32))
+
+
+def weld_vertices(verts):
+    """int32 [V] on verts' device: rep[v] = the smallest index whose position equals v's, coordinate by coordinate with
+    -0 == +0 (exact: one ulp apart is different); -1 for a vertex with a NaN or infinite coordinate (eslam_mesh_weld).
+    verts float32 [V,3] on the GPU."""
+    v = _mesh_gpu("verts", verts, torch.float32, 3)
+    dev = v.device
+    n = v.shape[0]
+    rep = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return rep
+    lib = _hip.lib()
+    ws = torch.empty(int(lib.eslam_mesh_weld_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(lib.eslam_mesh_weld(_hip.ptr(v), n, _hip.ptr(ws), _hip.ptr(rep), _hip.stream_handle(dev)), "eslam_mesh_weld")
+    return rep
+
+
+def mesh_components(faces, n_verts):
+    """int32 [n_verts] on faces' device: the smallest vertex index of every vertex's connected component, faces joined
+    through shared VERTICES (eslam_mesh_components); a vertex in no face labels itself.  faces [F,3] integer on the GPU;
+    an index outside [0, n_verts) raises ValueError."""
+    n_verts = int(n_verts)
+    if n_verts < 0 or n_verts > _hip.MESH_MAX_COUNT:
+        raise RuntimeError(f"mesh_components: {n_verts} vertices (0 .. 2^30)")
+    f = _mesh_faces(faces, n_verts)
+    dev = f.device
+    label = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    if n_verts == 0:
+        return label
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_mesh_components(_hip.ptr(f), f.shape[0], n_verts, _hip.ptr(label),
+                                                    _hip.stream_handle(dev)), "eslam_mesh_components")
+    return label
+
+
+def component_face_counts(faces, labels):
+    """int32 [V] on faces' device: at every component's label the number of its faces (a face counts where its first
+    corner's label points), 0 elsewhere (eslam_mesh_component_sizes; exact).  labels int32 [V] from mesh_components."""
+    lab = _mesh_gpu("labels", labels, torch.int32, 0)
+    n_verts = lab.shape[0]
+    f = _mesh_faces(faces, n_verts)
+    dev = f.device
+    if lab.device != dev:
+        raise RuntimeError(f"component_face_counts: faces on {dev}, labels on {lab.device}")
+    count = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    if n_verts == 0:
+        return count
+    if f.shape[0]:
+        lo, hi = lab.aminmax()
+        if int(lo) < 0 or int(hi) >= n_verts:
+            raise ValueError(f"labels: values span [{int(lo)}, {int(hi)}], the mesh has {n_verts} vertices")
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_mesh_component_sizes(_hip.ptr(f), f.shape[0], _hip.ptr(lab), n_verts, _hip.ptr(count),
+                                                         _hip.stream_handle(dev)), "eslam_mesh_component_sizes")
+    return count
+
+
 def sample_surface(verts, faces, n, seed=0):
     """(samples float64 [n,3], face_index int64 [n]) on verts' device, as trimesh.sample.sample_surface: faces picked
     with probability proportional to their area (float64 areas, cumulative sum, searchsorted of u * total, left side),

@@ -18,6 +18,8 @@ Written under <output>/:
     mesh/NNNNN_mesh.ply        every mapping.mesh_freq frames, with its culled copy NNNNN_mesh_culled.ply; frame 0
                                skipped with mapping.no_mesh_on_first_frame
     mesh/final_mesh.ply        (final_mesh_eval_rec.ply with meshing.eval_rec) and its culled copy, at the end
+    mesh/*_culled_clean.ply    with meshing.clean_min_faces: N > 0 (ours; absent or 0 = off): every culled mesh once more
+                               without the connected components of fewer than N faces (tools/clean_mesh.py)
     ate.json                   eval_ate.evaluate of the estimated against the dataset's trajectory
     tracking_vis/NNNNN_IIII.jpg, mapping_vis/NNNNN_IIII.jpg
                                the visualisers' panels: frame NNNNN, iteration IIII, every vis_freq frames and
@@ -34,7 +36,8 @@ import torch
 from .. import checkpoint, eval_ate
 from ..scene import scene_from_config
 from ..slam import Slam, SlamConfig
-from .tools.cull_mesh import cull_mesh
+from .tools.clean_mesh import clean_mesh
+from .tools.cull_mesh import cull_mesh, culled_path
 from .utils.datasets import FrameStream, get_dataset
 from .utils.Frame_Visualizer import Frame_Visualizer
 from .utils.Mesher import Mesher
@@ -72,6 +75,7 @@ class ESLAM:
         self.no_log_on_first_frame = bool(m.get('no_log_on_first_frame', False))
         self.no_mesh_on_first_frame = bool(m.get('no_mesh_on_first_frame', False))
         self.eval_rec = bool(cfg['meshing']['eval_rec'])
+        self.clean_min_faces = int(cfg['meshing'].get('clean_min_faces', 0) or 0)
         self.render_eval_every = int((cfg.get('render_eval') or {}).get('every', 0) or 0)
         self.render_eval = None
         self.visualizers = {}
@@ -100,6 +104,8 @@ class ESLAM:
         if os.path.exists(mesh_out_file):                                # (no surface: get_mesh says so and writes nothing)
             est = torch.stack([c.detach().cpu() for c in s.estimate_c2w_list[:n_poses]], 0)
             cull_mesh(mesh_out_file, self.cfg, self.args, self.device, estimate_c2w_list=est)
+            if self.clean_min_faces > 0:
+                clean_mesh(culled_path(mesh_out_file), device=self.device, min_faces=self.clean_min_faces)
 
     def _on_frame(self, s, idx):
         """Mapper.py:437-446 for a frame the mapper has seen (its loop runs at mapped frames and at the last one)."""

@@ -7,8 +7,10 @@ frame runs in one HIP launch per chunk of frames (ops.cull_vertices), the mesh i
 Rule (cull_mesh.py:61-112): a vertex is seen when one frame sees it (the test of eslam_cull_vertices, with the depth test
 when cfg['meshing']['eval_rec']); faces whose three vertices were never seen are dropped, then the vertices no face
 references; both keep their order, vertex colours follow their vertices.
-Deviation: the reference ends with trimesh's process(), which also merges vertices at equal positions.  That step is
-skipped: the marching-cubes output of Mesher.get_mesh is already welded (one vertex per crossing edge).
+The reference ends with trimesh's process(), which also removes non-finite vertices and merges vertices at equal
+positions.  By default that step is skipped: the marching-cubes output of Mesher.get_mesh is already welded (one vertex per
+crossing edge).  merge_vertices=True (--merge_vertices) applies it (tools/clean_mesh.py, steps (a) and (d)), for meshes
+that come with one vertex per face corner.
 """
 import argparse
 import os
@@ -35,13 +37,18 @@ def compact(vertices, faces, colors, seen):
 
 
 def cull_mesh_arrays(vertices, faces, colors, frames, H, W, fx, fy, cx, cy, truncation, eval_rec, device="cuda:0",
-                     chunk=32):
+                     chunk=32, merge_vertices=False):
     """In-memory cull_mesh: frames are (idx, colour, depth, c2w) tuples, as the dataset readers and
-    synthscene.make_sequence yield them.  Returns (vertices, faces, colours) as numpy arrays."""
+    synthscene.make_sequence yield them.  Returns (vertices, faces, colours) as numpy arrays.  merge_vertices: the
+    reference's closing process() on the culled mesh (non-finite vertices removed, equal positions merged)."""
     dev = torch.device(device)
     v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float32)).to(dev)
     seen = ops.cull_vertices(v, ((fr[2], fr[3]) for fr in frames), (fx, fy, cx, cy), H, W, truncation, eval_rec, chunk)
-    return compact(vertices, faces, colors, seen.cpu().numpy())
+    out = compact(vertices, faces, colors, seen.cpu().numpy())
+    if merge_vertices:
+        from .clean_mesh import clean_mesh_arrays
+        out = clean_mesh_arrays(*out, merge_vertices=True, device=device)[:3]
+    return out
 
 
 def _update(dst, src):
@@ -75,10 +82,10 @@ def culled_path(mesh_file):
     return mesh_file[:-len(ext) - 1] + '_culled.' + ext
 
 
-def cull_mesh(mesh_file, cfg, args, device, estimate_c2w_list=None):
+def cull_mesh(mesh_file, cfg, args, device, estimate_c2w_list=None, merge_vertices=False):
     """cull_mesh.py:36-113: cull the mesh to what the frames see, written next to it as <stem>_culled.<ext> (PLY).
     Frames come from datasets.get_dataset(cfg, args, 1, device); with estimate_c2w_list, its length is the frame count
-    and its poses replace the reader's."""
+    and its poses replace the reader's.  merge_vertices: see cull_mesh_arrays."""
     from ..utils.datasets import get_dataset
     frame_reader = get_dataset(cfg, args, 1, device=device)
     eval_rec = cfg['meshing']['eval_rec']
@@ -94,7 +101,8 @@ def cull_mesh(mesh_file, cfg, args, device, estimate_c2w_list=None):
             yield idx, color, torch.as_tensor(depth), torch.as_tensor(c2w)
 
     vertices, faces, colors = read_ply(mesh_file)
-    out = cull_mesh_arrays(vertices, faces, colors, frames(), H, W, fx, fy, cx, cy, truncation, eval_rec, device)
+    out = cull_mesh_arrays(vertices, faces, colors, frames(), H, W, fx, fy, cx, cy, truncation, eval_rec, device,
+                           merge_vertices=merge_vertices)
     write_ply(culled_path(mesh_file), *out)
 
 
@@ -102,6 +110,8 @@ if __name__ == '__main__':
     parser = argparse.ArgumentParser(description='Arguments to cull the mesh.')
     parser.add_argument('config', type=str, help='path to the config file')
     parser.add_argument('--input_mesh', type=str, help='path to the mesh to be culled')
+    parser.add_argument('--merge_vertices', action='store_true',
+                        help="end as the reference's process() does: remove non-finite vertices, merge equal positions")
     args = parser.parse_args()
     args.input_folder = None
-    cull_mesh(args.input_mesh, load_config(args.config, 'configs/ESLAM.yaml'), args, 'cuda')
+    cull_mesh(args.input_mesh, load_config(args.config, 'configs/ESLAM.yaml'), args, 'cuda', merge_vertices=args.merge_vertices)
