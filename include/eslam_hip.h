@@ -236,6 +236,40 @@ int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* d
                           const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o, float* g_rays_d,
                           const int32_t* ray_order, void* workspace, eslam_stream_t stream);
 
+/* The saved first hidden layer (float32 planes).  The four entries above with one more pointer in front of `stream`:
+ * hidden, eslam_saved_hidden_floats(R, S) = 2 * R * ceil(S / 16) * 256 floats (128 bytes per sample when S is a multiple
+ * of 16), or NULL.  The forward entries fill it with h1 = relu(W1 . feat + b1) of both decoders as their kernel holds it - block
+ * (decoder d, ray, sb = 16 samples) at float offset ((d * R + ray) * ceil(S / 16) + sb) * 256, unit 4q + i of point r of the block
+ * at (16 q + r) * 4 + i, blocks stored whole - and need feat with it; R * ceil(S / 16) * 2048 < 2^32 - 256 (32-bit byte
+ * offsets), else an error.  The backward entries, given the buffer the forward pass of the same call filled, read h1 from it
+ * instead of recomputing it from feat (16 of a block's 52 MFMAs): every output has the same bits.  NULL: the entries above,
+ * which are these with NULL.  Planes with data_f16 (mixed precision) ignore the pointer.                                   */
+int64_t eslam_saved_hidden_floats(int64_t R, int S);
+int eslam_render_fwd_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                       const float* rays_o, const float* rays_d, const float* z_vals, int R, int S, float* depth,
+                       float* rgb, float* sdf, float* raw_rgb, float* feat, const int32_t* ray_order,
+                       uint32_t* rng_bump, float* hidden, eslam_stream_t stream);
+int eslam_render_fwd_loss_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                            const float* rays_o, const float* rays_d, const float* z_vals, int R, int S, float* depth,
+                            float* rgb, float* sdf, float* raw_rgb, float* feat, const int32_t* ray_order,
+                            const float* gt_depth, const float* gt_color, double truncation, const float* weights5_host,
+                            const uint8_t* ray_mask, float* scratch, float* acc, float* loss, uint32_t* rng_bump,
+                            float* hidden, eslam_stream_t stream);
+int eslam_render_bwd_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                       const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                       const float* sdf, const float* raw_rgb, const float* feat, const float* g_depth,
+                       const float* g_rgb, const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o,
+                       float* g_rays_d, const int32_t* ray_order, void* workspace, const float* hidden,
+                       eslam_stream_t stream);
+int eslam_render_bwd_loss_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                            const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                            const float* sdf, const float* raw_rgb, const float* feat, const float* depth,
+                            const float* rgb, const float* gt_depth, const float* gt_color, double truncation,
+                            const float* weights5_host, const uint8_t* ray_mask, const float* acc,
+                            const float* upstream, float* loss_out, const float* g_depth, const float* g_rgb,
+                            const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o, float* g_rays_d,
+                            const int32_t* ray_order, void* workspace, const float* hidden, eslam_stream_t stream);
+
 /* Decoder-only query.  Replaces src/networks/decoders.py:127-146 (Decoders.forward), the entry used by
  * src/utils/Mesher.py:151 on up to 500k points.  pts [N,3] world coordinates -> raw [N,4] = (r,g,b,sdf).
  * flags: ESLAM_DECODE_SDF_ONLY evaluates geometry planes + SDF decoder only (decoders.py:87-105) and writes
@@ -693,6 +727,9 @@ int eslam_scatter_bundle_samples(int64_t n, int S, int render);
  * Host bookkeeping, no launch.  FOR TESTS ONLY: one unsynchronised process-wide value written at dispatch - with concurrent
  * callers it is racy and names only the last dispatch; no caller may branch on it. */
 int eslam_last_backward_rank16(void);
+/* The same kind of bookkeeping, FOR TESTS ONLY: 1 = that backward read the forward pass's saved first hidden layer
+ * (eslam_render_bwd_h / _bwd_loss_h with a buffer, float32 planes), 0 = it recomputed the layer from the features. */
+int eslam_last_backward_saved_hidden(void);
 
 /* Host-side helper of the Python layer (no reference counterpart): `waiter` waits for the work enqueued on `signaler` so
  * far - the fork / join of the side stream the ray ordering (eslam_ray_order, what the backward's scatter bundles by) runs

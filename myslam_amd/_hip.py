@@ -100,6 +100,15 @@ SIGNATURES = {
                               _vp, _vp, _vp]),
     "eslam_render_bwd_loss": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _BP, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the same four with the saved first hidden layer (one more pointer in front of the stream), and its size in floats
+    "eslam_saved_hidden_floats": (_i64, [_i64, _i]),
+    "eslam_render_fwd_h": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eslam_render_fwd_loss_h": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _BP, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eslam_render_bwd_h": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp]),
+    "eslam_render_bwd_loss_h": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _BP, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_decode_fwd": (_i, [_PP, _DP, _BP, _vp, _i64, _i, _vp, _vp, _vp]),
     "eslam_sdf_grid": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _vp, _vp]),
     "eslam_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
@@ -149,6 +158,7 @@ SIGNATURES = {
     "eslam_deterministic": (_i, []),
     "eslam_scatter_bundle_samples": (_i, [_i64, _i, _i]),
     "eslam_last_backward_rank16": (_i, []),
+    "eslam_last_backward_saved_hidden": (_i, []),
     "eslam_loss_scratch_floats": (_i64, [_i64]),
     "eslam_loss_scratch_reset": (_i, [_vp, _i64, _vp]),
     "eslam_loss_value": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _BP, _vp, _vp, _vp, _vp, _vp]),

@@ -94,6 +94,15 @@ __device__ __forceinline__ void load_dec_frag(DecFrag& f, const float* L, int r,
     f.b3 = *(const float4_t*)(L + DEC_B3);
 }
 
+// the second hidden layer from the first: also on its own, for a backward pass that reads the forward pass's saved h1
+__device__ __forceinline__ void mlp_hidden2(const DecFrag& f, const float4_t& h1, float4_t& h2) {
+    float4_t a2 = f.b2;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) a2 = mfma16(f.w2[ks], h1[ks], a2);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h2[i] = fmaxf(a2[i], 0.0f);
+}
+
 // hidden activations of one 16-point block: h^T rows 4q+reg, col = point r
 __device__ __forceinline__ void mlp_hidden(const DecFrag& f, const float feat[16], float4_t& h1, float4_t& h2) {
     float4_t a1 = f.b1;
@@ -101,12 +110,13 @@ __device__ __forceinline__ void mlp_hidden(const DecFrag& f, const float feat[16
     for (int ks = 0; ks < 16; ++ks) a1 = mfma16(f.w1[ks], feat[ks], a1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) h1[i] = fmaxf(a1[i], 0.0f);
-    float4_t a2 = f.b2;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) a2 = mfma16(f.w2[ks], h1[ks], a2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) h2[i] = fmaxf(a2[i], 0.0f);
+    mlp_hidden2(f, h1, h2);
 }
+
+// The saved first hidden layer H [2][R][SB][256] floats, SB = ceil(S / 16): one 1 KB block per decoder, ray and 16-point
+// block, MFMA-role lane l owning floats [4l, 4l + 4) - unit 4q + i of point r at (16q + r) * 4 + i - exactly the float4_t
+// mlp_hidden returns.  Blocks past a chunk's last valid point are stored whole (clamped duplicate points).
+__device__ __forceinline__ int64_t hidden_blocks(int S) { return (S + 15) >> 4; }
 
 // output layer of block b accumulated into the tile-wide accumulator `out` (sample role on return)
 __device__ __forceinline__ void mlp_out_accum(const DecFrag& f, const float4_t& h2, int b, int r, float4_t& out) {
@@ -260,6 +270,12 @@ __device__ __forceinline__ void store_features_buffer(__amdgpu_buffer_rsrc_t rsr
     for (int j = 0; j < 4; ++j)          // piece j: level j >> 1, half j & 1 - the order of store_features
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_bits, (float4_t){feat[4 * j], feat[4 * j + 1], feat[4 * j + 2], feat[4 * j + 3]}),
                                                rsrc, (int)byte_off + 64 * j, 0, 2);      // aux bit 1 = nt
+}
+
+// One block of the saved first hidden layer (see hidden_blocks): one always-issued, streamed 16-byte store per lane, 1 KB
+// contiguous per wave.  A descriptor of zero length (no buffer given) makes the hardware drop it.
+__device__ __forceinline__ void store_hidden_buffer(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off, const float4_t& h1) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_bits, h1), rsrc, (int)byte_off, 0, 2);      // aux bit 1 = nt
 }
 
 // the same 16 values read back (backward pass), gather role

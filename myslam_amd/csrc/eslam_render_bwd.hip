@@ -113,11 +113,18 @@ struct RayBwdIn {                  // MODE >= 1: what the composite backward of 
 // registers to the gather role and one store).  The block's g_z1 is stored, gz[2][N][16]
 // (decoder-major: a 128-byte line holds two consecutive samples of one ray), in the region g_feat occupies otherwise and a
 // quarter of its size; scatter_sort_kernel<GZ> sums it per texel cell and expands each cell's sums once.
-template <int MODE, bool WGRAD, bool LOWP, bool GZ = false>
+// SAVEDH (float32 rays, the forward pass saved its first hidden layer: `hid`, layout at hidden_blocks in eslam_decode_tile.h):
+// h1 is READ - one 16-byte load per lane and block, requested a block ahead with the block's feature rows - instead of being
+// rebuilt from the features: 16 of a block's 52 dependent MFMAs (GZ), the 16 ds_bpermute that moved the features to the MFMA
+// role and the 16 registers of the W1 fragment go; h2 is still recomputed from h1 (4 MFMAs).  Same instructions on the same
+// values as in the forward pass, so every output keeps its bits.  The features are still read for the g_W1 contraction (through
+// the wave-private LDS tile, gather role); with frozen decoders (WGRAD = false) they are not read at all.
+template <int MODE, bool WGRAD, bool LOWP, bool GZ = false, bool SAVEDH = false>
 __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t dec, const float* __restrict__ feat,
                                                       const float* __restrict__ g_o, int64_t N,
                                                       float* __restrict__ g_feat, float* __restrict__ slabs,
-                                                      const RayBwdIn rb, const LossGradIn li) {
+                                                      const RayBwdIn rb, const LossGradIn li,
+                                                      const float* __restrict__ hid) {
     __shared__ __attribute__((aligned(16))) float wlds[2 * DEC_LDS];
     __shared__ __attribute__((aligned(16))) float tiles[4][4][16 * TP];   // per wave: gz1, gz2, h1, h2 (as [pt][j])
     __shared__ __attribute__((aligned(16))) float gtile[4][64 * 4];       // per wave: g_o of the tile [pt][o]
@@ -128,6 +135,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
     __syncthreads();
 
     static_assert(!GZ || (!LOWP && MODE != 0), "GZ: float32 rays only");
+    static_assert(!SAVEDH || (!LOWP && MODE != 0), "SAVEDH: float32 rays only");
+    constexpr bool ROWS = !SAVEDH || WGRAD;           // the block's feature rows are read
     const int d = blockIdx.y;                         // 0 = sdf decoder, 1 = colour decoder
     const int nout = d ? 3 : 1;
     const float* L = wlds + d * DEC_LDS;
@@ -217,11 +226,17 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
         v[3] = *(const float4_t*)(fp + 48);
     };
 #define TOUCH(x) asm volatile("" :: "v"(x))
-#define TOUCH_ROWS { TOUCH(fnext[0]); TOUCH(fnext[1]); TOUCH(fnext[2]); TOUCH(fnext[3]); }
+#define TOUCH_ROWS { if (ROWS) { TOUCH(fnext[0]); TOUCH(fnext[1]); TOUCH(fnext[2]); TOUCH(fnext[3]); } if (SAVEDH) TOUCH(hnext); }
     // fnext: the rows of the block that comes next - of this tile, or block 0 of the tile at p0_next, requested by this tile's
     // last block in front of its stores and waited for by the CALLER (TOUCH_ROWS) before it requests anything
     float4_t fnext[4];
-    auto tile_bwd = [&](const int64_t p0, const int nvalid, const float go[4], const int64_t p0_next) {
+    // SAVEDH: the saved h1 of the same block, requested at the same site: hb = the tile's first block in `hid`, hb_next that of
+    // the tile that comes next (a block past the buffer's end - the wave has no further ray - is clamped, as rows past N are)
+    float4_t hnext = (float4_t){0.f, 0.f, 0.f, 0.f};
+    const int64_t hb_last = SAVEDH ? 2 * (int64_t)rb.R * hidden_blocks(rb.S) - 1 : 0;
+    auto load_hidden = [&](const int64_t hblk) { return *(const float4_t*)(hid + min(hblk, hb_last) * 256 + lane * 4); };
+    auto tile_bwd = [&](const int64_t p0, const int nvalid, const float go[4], const int64_t p0_next, const int64_t hb,
+                        const int64_t hb_next) {
         const int nblk = (nvalid + 15) >> 4;
         __builtin_assume(nblk >= 1);
 #pragma unroll
@@ -242,13 +257,17 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
 #pragma unroll 1
         for (int b = 0; b < nblk; ++b) {
             float ft[16];
+            if (ROWS) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                ft[i] = fnext[0][i]; ft[4 + i] = fnext[1][i]; ft[8 + i] = fnext[2][i]; ft[12 + i] = fnext[3][i];
+                for (int i = 0; i < 4; ++i) {
+                    ft[i] = fnext[0][i]; ft[4 + i] = fnext[1][i]; ft[8 + i] = fnext[2][i]; ft[12 + i] = fnext[3][i];
+                }
             }
+            const float4_t hsaved = hnext;
             // (two blocks ahead: 250 VGPRs, no faster.)  ONE request site with a selected address: two sites behind an if / else
             // made the compiler wait for vmcnt(0)
-            load_block(0, fnext, b + 1 < nblk ? p0 + 16 * (b + 1) : p0_next);
+            if (ROWS) load_block(0, fnext, b + 1 < nblk ? p0 + 16 * (b + 1) : p0_next);
+            if (SAVEDH) hnext = load_hidden(b + 1 < nblk ? hb + b + 1 : hb_next);
             // the same rows again in the "feature on the lane" layout of the g_W1 contraction (B operand): NOT re-read from
             // memory but handed over through a wave-private LDS tile, written here in the gather role and read back just before
             // the contraction.  A global re-read (L1 / L2 hits) was waited for in the middle of the block - behind the previous
@@ -266,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 for (int j = 0; j < 4; ++j) *(float4_t*)(T + 16 * j) = (float4_t){ft[4 * j], ft[4 * j + 1], ft[4 * j + 2], ft[4 * j + 3]};
             }
             if (LOWP) to_mfma_role<true, 8>(ft, lane);       // 8 registers of packed bf16 pairs
-            else to_mfma_role<true, 16>(ft, lane);
+            else if (!SAVEDH) to_mfma_role<true, 16>(ft, lane);
             float4_t h1, h2, gz1, gz2;
             const float4_t zero4 = (float4_t){0.f, 0.f, 0.f, 0.f};
             float gf[16];
@@ -306,7 +325,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 to_gather_role<true, 16>(gf, lane);
                 store_rows(p0, b, nvalid, gf);
             } else {
-            mlp_hidden(f, ft, h1, h2);
+            if (SAVEDH) { h1 = hsaved; mlp_hidden2(f, h1, h2); }
+            else mlp_hidden(f, ft, h1, h2);
 
             // g_h2^T = W3^T . g_o^T   (K = (block', o); only block' == b contributes)
             float4_t gh2 = (float4_t){0.f, 0.f, 0.f, 0.f};
@@ -412,11 +432,13 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 else { go[0] = g[0]; go[1] = g[1]; go[2] = g[2]; }
             }
             TOUCH_ROWS
-            tile_bwd(p0, nvalid, go, (tile + (int64_t)gridDim.x * 4) * 64);
+            tile_bwd(p0, nvalid, go, (tile + (int64_t)gridDim.x * 4) * 64, 0, 0);
         }
     } else {
         const int R = rb.R, S = rb.S;
         const int nchunk = (S + WAVE - 1) / WAVE;
+        const int64_t SB = hidden_blocks(S);
+        auto hidden_block = [&](int ray_, int c_) { return ((int64_t)d * R + ray_) * SB + 4 * c_; };      // chunk c_ starts at block 4 c_
         __builtin_assume(nchunk >= 1);             // (S >= 1 is checked at the launch; lets the compiler count a ray's stores)
         const float beta = rb.beta[0];
         LossW lw = {};
@@ -485,7 +507,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
             rin = load_ray(ray);
             cin = load_chunk(ray, nchunk - 1);
             pin = load_pa(ray);
-            load_block(0, fnext, (int64_t)ray * S + (nchunk - 1) * WAVE);
+            if (ROWS) load_block(0, fnext, (int64_t)ray * S + (nchunk - 1) * WAVE);
+            if (SAVEDH) hnext = load_hidden(hidden_block(ray, nchunk - 1));
         }
         dropped_stores();                                     // the waits below are counted by the compiler: see tile_bwd
 #define TOUCH_CHUNK(ci) { TOUCH(ci.sd); TOUCH(ci.z); TOUCH(ci.cr); TOUCH(ci.cg); TOUCH(ci.cb); TOUCH(ci.gs); }
@@ -551,7 +574,8 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const eslam_decoders_t 
                 else { go[0] = o[0]; go[1] = o[1]; go[2] = o[2]; }
                 // the tile after this one: the chunk in front of it, or the last chunk of the wave's next ray (rows past N are clamped)
                 tile_bwd(base + c * WAVE, min(WAVE, S - c * WAVE), go,
-                         c > 0 ? base + (c - 1) * WAVE : (int64_t)(ray + stride) * S + (nchunk - 1) * WAVE);
+                         c > 0 ? base + (c - 1) * WAVE : (int64_t)(ray + stride) * S + (nchunk - 1) * WAVE, hidden_block(ray, c),
+                         c > 0 ? hidden_block(ray, c - 1) : hidden_block(ray + stride, nchunk - 1));
                 if (c > 0) {
                     TOUCH_CHUNK(cn)
                     TOUCH_ROWS
@@ -933,12 +957,15 @@ extern "C" int64_t eslam_bwd_workspace_bytes(int64_t n_points) {
 // 1 when the last backward this process dispatched took the rank-16 pair, 0 when it wrote full-width rows (host bookkeeping)
 static int g_last_backward_rank16 = 0;
 extern "C" int eslam_last_backward_rank16(void) { return g_last_backward_rank16; }
+// 1 when it read the forward pass's saved first hidden layer, 0 when it recomputed it
+static int g_last_backward_saved_hidden = 0;
+extern "C" int eslam_last_backward_saved_hidden(void) { return g_last_backward_saved_hidden; }
 
 // mode 0: free points (g_o in the workspace); 1: rays, upstream gradients in rb; 2: rays, mapping-loss gradients from li
 static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, const Bound& bnd, const float* rays_o,
                       const float* rays_d, const float* z_or_pts, int64_t R, int S, int mode, const float* feat,
                       float* g_o, float* g_feat, float* slabs, const int* perm, float* g_dec, float* g_out_a, float* g_out_b,
-                      RayBwdIn rb, const LossGradIn* li, float* g_beta, hipStream_t st) {
+                      RayBwdIn rb, const LossGradIn* li, float* g_beta, const float* hid, hipStream_t st) {
     const bool render = mode != 0;
     const int64_t N = render ? R * S : R;
     PlaneSet ps;
@@ -959,7 +986,7 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     eslam_prof_begin(PROF_MLP_BWD, st);
 #define LAUNCH_MB(MD, WG, LP, ...) \
     hipLaunchKernelGGL((mlp_bwd_kernel<MD, WG, LP, ##__VA_ARGS__>), dim3(nwg, 2), dim3(256), 0, st, *dec, feat, g_o, N, g_feat, slabs, rb, \
-                       li ? *li : none)
+                       li ? *li : none, hid)
     const int lowp = eslam_planes_lowp(planes);
     if (lowp < 0) return 1;
     bool any_grad = false, all_grad = true;
@@ -976,7 +1003,17 @@ static int bwd_common(const eslam_plane_t* planes, const eslam_decoders_t* dec, 
     // mixed-precision kernels and deterministic mode (fixed point per CONTRIBUTION) keep the full-width rows.
     const bool gz = !lowp && render && any_grad && !g_out_a && !eslam_deterministic();
     g_last_backward_rank16 = gz ? 1 : 0;
-    if (gz) {
+    if (lowp || !render) hid = nullptr;        // (mixed precision and free points save no hidden layer)
+    g_last_backward_saved_hidden = hid ? 1 : 0;
+    if (hid) {                                 // float32 rays on the forward pass's saved h1
+        if (gz) {
+            if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, false, true, true); else LAUNCH_MB(1, false, false, true, true); }
+            else { if (g_dec) LAUNCH_MB(2, true, false, true, true); else LAUNCH_MB(2, false, false, true, true); }
+        }
+        else if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, false, false, true); else LAUNCH_MB(1, false, false, false, true); }
+        else { if (g_dec) LAUNCH_MB(2, true, false, false, true); else LAUNCH_MB(2, false, false, false, true); }
+    }
+    else if (gz) {
         if (mode == 1) { if (g_dec) LAUNCH_MB(1, true, false, true); else LAUNCH_MB(1, false, false, true); }
         else { if (g_dec) LAUNCH_MB(2, true, false, true); else LAUNCH_MB(2, false, false, true); }
     }
@@ -1045,7 +1082,7 @@ static int render_bwd_impl(const char* who, const eslam_plane_t* planes, const e
                            const float* bound6_host, const float* rays_o, const float* rays_d, const float* z_vals, int R,
                            int S, const float* sdf, const float* raw_rgb, const float* feat, const float* g_depth,
                            const float* g_rgb, const float* g_sdf, const LossGradIn* li, float* g_dec, float* g_beta,
-                           float* g_rays_o, float* g_rays_d, const int32_t* ray_order, void* workspace,
+                           float* g_rays_o, float* g_rays_d, const int32_t* ray_order, void* workspace, const float* hid,
                            eslam_stream_t stream) {
     if (R <= 0) return 0;
     if (S <= 0 || S > ESLAM_MAX_SAMPLES) {
@@ -1084,7 +1121,17 @@ static int render_bwd_impl(const char* who, const eslam_plane_t* planes, const e
     rb.z_vals = z_vals; rb.sdf = sdf; rb.raw_rgb = raw_rgb; rb.beta = dec->beta;
     rb.g_depth = g_depth; rb.g_rgb = g_rgb; rb.g_sdf = g_sdf; rb.R = R; rb.S = S;
     return bwd_common(planes, dec, bnd, rays_o, rays_d, z_vals, R, S, li ? 2 : 1, feat, g_o, g_feat, slabs, perm, g_dec,
-                      g_rays_o, g_rays_d, rb, li, g_beta, st);
+                      g_rays_o, g_rays_d, rb, li, g_beta, hid, st);
+}
+
+extern "C" int eslam_render_bwd_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                  const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                                  const float* sdf, const float* raw_rgb, const float* feat, const float* g_depth,
+                                  const float* g_rgb, const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o,
+                                  float* g_rays_d, const int32_t* ray_order, void* workspace, const float* hidden,
+                                  eslam_stream_t stream) {
+    return render_bwd_impl("eslam_render_bwd", planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, sdf, raw_rgb, feat,
+                           g_depth, g_rgb, g_sdf, nullptr, g_dec, g_beta, g_rays_o, g_rays_d, ray_order, workspace, hidden, stream);
 }
 
 extern "C" int eslam_render_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
@@ -1092,18 +1139,19 @@ extern "C" int eslam_render_bwd(const eslam_plane_t* planes, const eslam_decoder
                                 const float* sdf, const float* raw_rgb, const float* feat, const float* g_depth,
                                 const float* g_rgb, const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o,
                                 float* g_rays_d, const int32_t* ray_order, void* workspace, eslam_stream_t stream) {
-    return render_bwd_impl("eslam_render_bwd", planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, sdf, raw_rgb, feat,
-                           g_depth, g_rgb, g_sdf, nullptr, g_dec, g_beta, g_rays_o, g_rays_d, ray_order, workspace, stream);
+    return eslam_render_bwd_h(planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, sdf, raw_rgb, feat, g_depth, g_rgb, g_sdf,
+                              g_dec, g_beta, g_rays_o, g_rays_d, ray_order, workspace, nullptr, stream);
 }
 
-extern "C" int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
-                                     const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
-                                     const float* sdf, const float* raw_rgb, const float* feat, const float* depth,
-                                     const float* rgb, const float* gt_depth, const float* gt_color, double truncation,
-                                     const float* weights5_host, const uint8_t* ray_mask, const float* acc,
-                                     const float* upstream, float* loss_out, const float* g_depth, const float* g_rgb,
-                                     const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o, float* g_rays_d,
-                                     const int32_t* ray_order, void* workspace, eslam_stream_t stream) {
+extern "C" int eslam_render_bwd_loss_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                       const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                                       const float* sdf, const float* raw_rgb, const float* feat, const float* depth,
+                                       const float* rgb, const float* gt_depth, const float* gt_color, double truncation,
+                                       const float* weights5_host, const uint8_t* ray_mask, const float* acc,
+                                       const float* upstream, float* loss_out, const float* g_depth, const float* g_rgb,
+                                       const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o, float* g_rays_d,
+                                       const int32_t* ray_order, void* workspace, const float* hidden,
+                                       eslam_stream_t stream) {
     if (!depth || !rgb || !gt_depth || !gt_color || !weights5_host || !acc) {
         eslam_set_error("eslam_render_bwd_loss: null loss argument");
         return 1;
@@ -1114,7 +1162,20 @@ extern "C" int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_de
     li.tr = make_trunc(truncation);
     li.w = LossW{weights5_host[0], weights5_host[1], weights5_host[2], weights5_host[3], weights5_host[4]};
     return render_bwd_impl("eslam_render_bwd_loss", planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, sdf, raw_rgb,
-                           feat, g_depth, g_rgb, g_sdf, &li, g_dec, g_beta, g_rays_o, g_rays_d, ray_order, workspace, stream);
+                           feat, g_depth, g_rgb, g_sdf, &li, g_dec, g_beta, g_rays_o, g_rays_d, ray_order, workspace, hidden, stream);
+}
+
+extern "C" int eslam_render_bwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                     const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                                     const float* sdf, const float* raw_rgb, const float* feat, const float* depth,
+                                     const float* rgb, const float* gt_depth, const float* gt_color, double truncation,
+                                     const float* weights5_host, const uint8_t* ray_mask, const float* acc,
+                                     const float* upstream, float* loss_out, const float* g_depth, const float* g_rgb,
+                                     const float* g_sdf, float* g_dec, float* g_beta, float* g_rays_o, float* g_rays_d,
+                                     const int32_t* ray_order, void* workspace, eslam_stream_t stream) {
+    return eslam_render_bwd_loss_h(planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, sdf, raw_rgb, feat, depth, rgb, gt_depth,
+                                   gt_color, truncation, weights5_host, ray_mask, acc, upstream, loss_out, g_depth, g_rgb, g_sdf,
+                                   g_dec, g_beta, g_rays_o, g_rays_d, ray_order, workspace, nullptr, stream);
 }
 
 extern "C" int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
@@ -1139,5 +1200,5 @@ extern "C" int eslam_decode_bwd(const eslam_plane_t* planes, const eslam_decoder
     hipLaunchKernelGGL(decode_act_bwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, raw, g_raw, N, g_o);
     if (int rc = eslam_check_launch("decode_act_bwd_kernel")) return rc;
     return bwd_common(planes, dec, bnd, nullptr, nullptr, pts, N, 64, 0, feat, g_o, g_feat, slabs, nullptr, g_dec,
-                      g_pts, nullptr, RayBwdIn{}, nullptr, nullptr, st);
+                      g_pts, nullptr, RayBwdIn{}, nullptr, nullptr, nullptr, st);
 }

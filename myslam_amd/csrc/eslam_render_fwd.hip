@@ -41,8 +41,9 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
                                                          const float* __restrict__ z_vals, int R, int S,
                                                          float* __restrict__ depth_out, float* __restrict__ rgb_out,
                                                          float* __restrict__ sdf_out, float* __restrict__ raw_rgb_out,
-                                                         float* __restrict__ feat_out, const int* __restrict__ perm,
-                                                         const LossIn li, uint32_t* __restrict__ rng_bump) {
+                                                         float* __restrict__ feat_out, float* __restrict__ hid_out,
+                                                         const int* __restrict__ perm, const LossIn li,
+                                                         uint32_t* __restrict__ rng_bump) {
     // the samplers drew this iteration's random numbers from (seed, *rng_bump) before this kernel started
     // (eslam_sample_z_all_rng): advance the step for the next iteration (of a replayed graph)
     if (rng_bump && blockIdx.x == 0 && threadIdx.x == 0) rng_bump[0] += 1u;
@@ -58,6 +59,10 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
     const int gp = gather_point<CL>(lane), gq = gather_piece<CL>(lane);     // gather role
     // (R * S * 512 < 2^32 - 256 is checked at the launch when features are saved)
     const __amdgpu_buffer_rsrc_t frsrc = __builtin_amdgcn_make_buffer_rsrc((void*)feat_out, 0, (int)((unsigned)R * (unsigned)S * 512u), 0x00020000);
+    // the saved first hidden layer (float32 planes, SAVE): 2 R SB blocks of 1 KB, checked at the launch as well; no buffer given =
+    // a descriptor of zero length, whose stores the hardware drops
+    const int SB = (int)hidden_blocks(S);
+    const __amdgpu_buffer_rsrc_t hrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)hid_out, 0, hid_out ? (int)(2u * (unsigned)R * (unsigned)SB * 1024u) : 0, 0x00020000);
     float lv[A_COUNT];                     // LOSS: this lane's share of the accumulators
 #pragma unroll
     for (int k = 0; k < A_COUNT; ++k) lv[k] = 0.0f;
@@ -134,6 +139,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
                     load_dec_frag(f, wlds + d * DEC_LDS + oz0, r, q);
                     float4_t h1, h2;
                     mlp_hidden(f, feat, h1, h2);
+                    if (SAVE) store_hidden_buffer(hrsrc, (unsigned)((d * R + ray) * SB + (c0 >> 4) + b) * 1024u + (unsigned)lane * 16u, h1);
                     mlp_out_accum(f, h2, b, r, out[d]);
                     continue;
                 }
@@ -163,6 +169,7 @@ __global__ __launch_bounds__(256, FWD_WAVES) void render_fwd_kernel(const PlaneS
                 load_dec_frag(f, wlds + d * DEC_LDS + oz0, r, q);
                 float4_t h1, h2;
                 mlp_hidden(f, feat, h1, h2);
+                if (SAVE) store_hidden_buffer(hrsrc, (unsigned)((d * R + ray) * SB + (c0 >> 4) + b) * 1024u + (unsigned)lane * 16u, h1);
                 mlp_out_accum(f, h2, b, r, out[d]);
             }
         }
@@ -436,7 +443,7 @@ static Bound make_bound(const float* b6) {
 
 static int render_fwd_common(const char* who, const eslam_plane_t* planes, const eslam_decoders_t* dec,
                              const float* bound6_host, const float* rays_o, const float* rays_d, const float* z_vals,
-                             int R, int S, float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat,
+                             int R, int S, float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat, float* hid,
                              const int32_t* ray_order, const LossIn* li, uint32_t* rng_bump, eslam_stream_t stream) {
     if (R <= 0) return 0;
     if (S <= 0 || S > ESLAM_MAX_SAMPLES) {
@@ -449,6 +456,15 @@ static int render_fwd_common(const char* who, const eslam_plane_t* planes, const
     }
     if ((raw_rgb == nullptr) != (feat == nullptr)) {
         eslam_set_error("%s: raw_rgb and feat must both be given or both be NULL", who);
+        return 1;
+    }
+    if (hid && !feat) {
+        eslam_set_error("%s: the hidden layer is saved beside the features: feat is NULL", who);
+        return 1;
+    }
+    if (hid && eslam_saved_hidden_floats(R, S) * 4 >= ((int64_t)1 << 32) - 256) {       // 32-bit byte offsets, as the features
+        eslam_set_error("%s: %lld rays of %d samples exceed the 32-bit offset range of the saved hidden layer: split the batch", who,
+                        (long long)R, S);
         return 1;
     }
     if (eslam_validate_planes(planes, 0, NPL)) return 1;
@@ -476,15 +492,16 @@ static int render_fwd_common(const char* who, const eslam_plane_t* planes, const
     dim3 grid(nwg), block(256);
     hipStream_t st = (hipStream_t)stream;
     const LossIn none = {};
-#define LAUNCH(CLv, SV, LS)                                                                                             \
-    hipLaunchKernelGGL((render_fwd_kernel<CLv, SV, LS, false>), grid, block, 0, st, ps, *dec, bnd, rays_o, rays_d, z_vals, R, \
-                       S, depth, rgb, sdf, raw_rgb, feat, (const int*)ray_order, LS ? *li : none, rng_bump)
-#define LAUNCH_LP(SV, LS)                                                                                               \
-    hipLaunchKernelGGL((render_fwd_kernel<true, SV, LS, true>), grid, block, 0, st, ps, *dec, bnd, rays_o, rays_d, z_vals, R, \
-                       S, depth, rgb, sdf, raw_rgb, feat, (const int*)ray_order, LS ? *li : none, rng_bump)
-    eslam_prof_begin(PROF_RENDER_FWD, st);
     const int lowp = eslam_planes_lowp(planes);
     if (lowp < 0) return 1;
+    float* hidp = lowp ? nullptr : hid;       // (the mixed-precision kernels save no hidden layer)
+#define LAUNCH(CLv, SV, LS)                                                                                             \
+    hipLaunchKernelGGL((render_fwd_kernel<CLv, SV, LS, false>), grid, block, 0, st, ps, *dec, bnd, rays_o, rays_d, z_vals, R, \
+                       S, depth, rgb, sdf, raw_rgb, feat, hidp, (const int*)ray_order, LS ? *li : none, rng_bump)
+#define LAUNCH_LP(SV, LS)                                                                                               \
+    hipLaunchKernelGGL((render_fwd_kernel<true, SV, LS, true>), grid, block, 0, st, ps, *dec, bnd, rays_o, rays_d, z_vals, R, \
+                       S, depth, rgb, sdf, raw_rgb, feat, hidp, (const int*)ray_order, LS ? *li : none, rng_bump)
+    eslam_prof_begin(PROF_RENDER_FWD, st);
     if (lowp) {
         if (li) { if (save) LAUNCH_LP(true, true); else LAUNCH_LP(false, true); }
         else { if (save) LAUNCH_LP(true, false); else LAUNCH_LP(false, false); }
@@ -505,20 +522,34 @@ static int render_fwd_common(const char* who, const eslam_plane_t* planes, const
     return eslam_check_launch("render_fwd_kernel");
 }
 
+extern "C" int64_t eslam_saved_hidden_floats(int64_t R, int S) {
+    if (R < 0 || S < 0) return -1;
+    return 2 * R * (((int64_t)S + 15) >> 4) * 256;
+}
+
+extern "C" int eslam_render_fwd_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                  const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                                  float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat,
+                                  const int32_t* ray_order, uint32_t* rng_bump, float* hidden, eslam_stream_t stream) {
+    return render_fwd_common("eslam_render_fwd", planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, depth, rgb, sdf,
+                             raw_rgb, feat, hidden, ray_order, nullptr, rng_bump, stream);
+}
+
 extern "C" int eslam_render_fwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                                 const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
                                 float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat,
                                 const int32_t* ray_order, uint32_t* rng_bump, eslam_stream_t stream) {
-    return render_fwd_common("eslam_render_fwd", planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, depth, rgb, sdf,
-                             raw_rgb, feat, ray_order, nullptr, rng_bump, stream);
+    return eslam_render_fwd_h(planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, depth, rgb, sdf, raw_rgb, feat, ray_order,
+                              rng_bump, nullptr, stream);
 }
 
-extern "C" int eslam_render_fwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
-                                     const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
-                                     float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat,
-                                     const int32_t* ray_order, const float* gt_depth, const float* gt_color,
-                                     double truncation, const float* weights5_host, const uint8_t* ray_mask,
-                                     float* scratch, float* acc, float* loss, uint32_t* rng_bump, eslam_stream_t stream) {
+extern "C" int eslam_render_fwd_loss_h(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                       const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                                       float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat,
+                                       const int32_t* ray_order, const float* gt_depth, const float* gt_color,
+                                       double truncation, const float* weights5_host, const uint8_t* ray_mask,
+                                       float* scratch, float* acc, float* loss, uint32_t* rng_bump, float* hidden,
+                                       eslam_stream_t stream) {
     if (!gt_depth || !gt_color || !weights5_host || !scratch || !acc) {
         eslam_set_error("eslam_render_fwd_loss: null loss argument");
         return 1;
@@ -534,7 +565,18 @@ extern "C" int eslam_render_fwd_loss(const eslam_plane_t* planes, const eslam_de
     li.tr = make_trunc(truncation);
     li.w = LossW{weights5_host[0], weights5_host[1], weights5_host[2], weights5_host[3], weights5_host[4]};
     return render_fwd_common("eslam_render_fwd_loss", planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, depth, rgb,
-                             sdf, raw_rgb, feat, ray_order, &li, rng_bump, stream);
+                             sdf, raw_rgb, feat, hidden, ray_order, &li, rng_bump, stream);
+}
+
+extern "C" int eslam_render_fwd_loss(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                     const float* rays_o, const float* rays_d, const float* z_vals, int R, int S,
+                                     float* depth, float* rgb, float* sdf, float* raw_rgb, float* feat,
+                                     const int32_t* ray_order, const float* gt_depth, const float* gt_color,
+                                     double truncation, const float* weights5_host, const uint8_t* ray_mask,
+                                     float* scratch, float* acc, float* loss, uint32_t* rng_bump, eslam_stream_t stream) {
+    return eslam_render_fwd_loss_h(planes, dec, bound6_host, rays_o, rays_d, z_vals, R, S, depth, rgb, sdf, raw_rgb, feat, ray_order,
+                                   gt_depth, gt_color, truncation, weights5_host, ray_mask, scratch, acc, loss, rng_bump, nullptr,
+                                   stream);
 }
 
 extern "C" int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,

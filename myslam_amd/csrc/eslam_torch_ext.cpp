@@ -122,6 +122,14 @@ void relayout(const std::vector<Tensor>& src, const std::vector<Tensor>& dst, in
     check(eslam_planes_relayout(a, b, field, st), "eslam_planes_relayout");
 }
 
+// The buffer a backward reads the first hidden layer from: refused when missing or short, before anything is launched.
+const float* require_saved_hidden(const Tensor& h, int64_t R, int64_t S) {
+    const int64_t want = eslam_saved_hidden_floats(R, (int)S);
+    TORCH_CHECK(h.defined() && h.scalar_type() == at::kFloat && h.is_contiguous() && h.numel() >= want,
+                "saved hidden layer: ", h.defined() ? h.numel() : 0, " elements, ", want, " contiguous float32 needed for ", R, " x ", S, " samples");
+    return h.data_ptr<float>();
+}
+
 class RenderNode : public torch::autograd::Function<RenderNode> {
 public:
     // inputs: rays_o, rays_d, beta, 12 planes, 12 decoder tensors  (27 tensors; everything else rides in `io`)
@@ -136,6 +144,8 @@ public:
         // kernels run on channels-last scratch filled here, and the backward hands the gradients back in the planes' own strides
         // (what ops.ChannelsLastFn does around the Python path; nothing is kept across calls: src/Mapper.py:254-266)
         bool relayout = false;
+        // save the decoders' first hidden layer for the backward (ops.saved_hidden_on()); off: the backward recomputes it
+        bool saved_hidden = true;
     };
 
     static variable_list forward(AutogradContext* ctx, at::TensorList in, const IO& io) {
@@ -159,10 +169,11 @@ public:
         const bool needs = io.needs, planes_grad = io.planes_grad;
         auto opt = rays_o.options();
         Tensor z = at::empty({R, S}, opt), depth = at::empty({R}, opt), rgb = at::empty({R, 3}, opt), sdf = at::empty({R, S}, opt);
-        Tensor raw_rgb, feat, perm, acc, value;
+        Tensor raw_rgb, feat, hid, perm, acc, value;
         if (needs) {
             raw_rgb = at::empty({R, S, 3}, opt);
             feat = at::empty({R * S, 128}, opt);
+            if (io.saved_hidden && R > 0) hid = at::empty({eslam_saved_hidden_floats(R, (int)S)}, opt);
             perm = at::empty({planes_grad ? ESLAM_RAY_ORDER_WORDS(R) : 0}, opt.dtype(at::kInt));     // the scatter's bundling orders: only planes with a gradient need them
         }
         if (io.relayout && R > 0) {
@@ -203,20 +214,22 @@ public:
             value = at::empty({}, opt);
             const Tensor gc = io.loss.gt_color.contiguous();
             const uint8_t* mask = io.loss.ray_mask.defined() ? (const uint8_t*)io.loss.ray_mask.data_ptr() : nullptr;
-            check(eslam_render_fwd_loss(pd, &dd, io.cfg.bound_decode.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),
+            check(eslam_render_fwd_loss_h(pd, &dd, io.cfg.bound_decode.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),
                                         z.data_ptr<float>(), (int)R, (int)S, depth.data_ptr<float>(), rgb.data_ptr<float>(),
                                         sdf.data_ptr<float>(), needs ? raw_rgb.data_ptr<float>() : nullptr,
                                         needs ? feat.data_ptr<float>() : nullptr, nullptr, gd.data_ptr<float>(), gc.data_ptr<float>(),
                                         io.cfg.truncation, io.loss.weights5.data(), mask, io.loss.scratch.data_ptr<float>(),
-                                        acc.data_ptr<float>(), value.data_ptr<float>(), bump, st), "eslam_render_fwd_loss");
+                                        acc.data_ptr<float>(), value.data_ptr<float>(), bump, hid.defined() ? hid.data_ptr<float>() : nullptr, st),
+                  "eslam_render_fwd_loss");
             ctx->saved_data["gt_color"] = gc;
             if (io.loss.ray_mask.defined()) ctx->saved_data["ray_mask"] = io.loss.ray_mask;
             ctx->saved_data["acc"] = acc;
             ctx->saved_data["w5"] = std::vector<double>(io.loss.weights5.begin(), io.loss.weights5.end());
         } else if (R > 0) {
-            check(eslam_render_fwd(pd, &dd, io.cfg.bound_decode.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), z.data_ptr<float>(),
+            check(eslam_render_fwd_h(pd, &dd, io.cfg.bound_decode.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), z.data_ptr<float>(),
                                    (int)R, (int)S, depth.data_ptr<float>(), rgb.data_ptr<float>(), sdf.data_ptr<float>(),
-                                   needs ? raw_rgb.data_ptr<float>() : nullptr, needs ? feat.data_ptr<float>() : nullptr, nullptr, bump, st),
+                                   needs ? raw_rgb.data_ptr<float>() : nullptr, needs ? feat.data_ptr<float>() : nullptr, nullptr, bump,
+                                   hid.defined() ? hid.data_ptr<float>() : nullptr, st),
                   "eslam_render_fwd");
         }
         if (side) check(eslam_stream_wait(st, side), "eslam_stream_wait");      // join behind the forward kernel
@@ -224,7 +237,9 @@ public:
             variable_list saved = {rays_o, rays_d, z, sdf, raw_rgb, feat, perm, beta, depth, rgb, gd};
             saved.insert(saved.end(), planes.begin(), planes.end());
             saved.insert(saved.end(), params.begin(), params.end());
+            if (hid.defined()) saved.push_back(hid);
             ctx->save_for_backward(saved);
+            ctx->saved_data["saved_hidden"] = hid.defined();
             ctx->saved_data["with_loss"] = with_loss;
             ctx->saved_data["relayout"] = io.relayout && R > 0;
             ctx->saved_data["truncation"] = io.cfg.truncation;
@@ -244,11 +259,13 @@ public:
 
     static variable_list backward(AutogradContext* ctx, variable_list g) {
         auto saved = ctx->get_saved_variables();
-        TORCH_CHECK(saved.size() == 35, "eslam_torch_ext: expected 35 saved tensors, got ", saved.size());
+        const bool saved_hidden = ctx->saved_data["saved_hidden"].toBool();
+        TORCH_CHECK(saved.size() == (saved_hidden ? 36u : 35u), "eslam_torch_ext: expected ", saved_hidden ? 36 : 35, " saved tensors, got ", saved.size());
         const Tensor &rays_o = saved[0], &rays_d = saved[1], &z = saved[2], &sdf = saved[3], &raw_rgb = saved[4], &feat = saved[5],
                      &perm = saved[6], &beta = saved[7], &depth = saved[8], &rgb = saved[9], &gd = saved[10];
         std::vector<Tensor> planes(saved.begin() + 11, saved.begin() + 23), params(saved.begin() + 23, saved.begin() + 35);
         const int64_t R = z.size(0), S = z.size(1);
+        const float* hid = saved_hidden ? require_saved_hidden(saved[35], R, S) : nullptr;
         const int dev = rays_o.get_device();
         c10::hip::HIPGuard guard(dev);
         hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
@@ -298,21 +315,21 @@ public:
             auto w5d = ctx->saved_data["w5"].toDoubleVector();
             float w5[5];
             for (int i = 0; i < 5; ++i) w5[i] = (float)w5d[i];
-            check(eslam_render_bwd_loss(pd, &dd, bound, rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), z.data_ptr<float>(), (int)R, (int)S,
+            check(eslam_render_bwd_loss_h(pd, &dd, bound, rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), z.data_ptr<float>(), (int)R, (int)S,
                                         sdf.data_ptr<float>(), raw_rgb.data_ptr<float>(), feat.data_ptr<float>(), depth.data_ptr<float>(),
                                         rgb.data_ptr<float>(), gd.data_ptr<float>(), gc.data_ptr<float>(), truncation, w5, mask,
                                         acc.data_ptr<float>(), up.data_ptr<float>(), nullptr, gdep.defined() ? gdep.data_ptr<float>() : nullptr,
                                         grgb.defined() ? grgb.data_ptr<float>() : nullptr, gsdf.defined() ? gsdf.data_ptr<float>() : nullptr,
                                         need_dec ? g_dec.data_ptr<float>() : nullptr, need_beta ? g_beta.data_ptr<float>() : nullptr,
                                         need_rays ? g_ro.data_ptr<float>() : nullptr, need_rays ? g_rd.data_ptr<float>() : nullptr,
-                                        perm.numel() ? perm.data_ptr<int32_t>() : nullptr, ws.data_ptr(), st), "eslam_render_bwd_loss");
+                                        perm.numel() ? perm.data_ptr<int32_t>() : nullptr, ws.data_ptr(), hid, st), "eslam_render_bwd_loss");
         } else {
-            check(eslam_render_bwd(pd, &dd, bound, rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), z.data_ptr<float>(), (int)R, (int)S,
+            check(eslam_render_bwd_h(pd, &dd, bound, rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), z.data_ptr<float>(), (int)R, (int)S,
                                    sdf.data_ptr<float>(), raw_rgb.data_ptr<float>(), feat.data_ptr<float>(), gdep.defined() ? gdep.data_ptr<float>() : nullptr,
                                    grgb.defined() ? grgb.data_ptr<float>() : nullptr, gsdf.defined() ? gsdf.data_ptr<float>() : nullptr,
                                    need_dec ? g_dec.data_ptr<float>() : nullptr, need_beta ? g_beta.data_ptr<float>() : nullptr,
                                    need_rays ? g_ro.data_ptr<float>() : nullptr, need_rays ? g_rd.data_ptr<float>() : nullptr,
-                                   perm.numel() ? perm.data_ptr<int32_t>() : nullptr, ws.data_ptr(), st), "eslam_render_bwd");
+                                   perm.numel() ? perm.data_ptr<int32_t>() : nullptr, ws.data_ptr(), hid, st), "eslam_render_bwd");
         }
         variable_list out(28);             // 27 tensor inputs + the IO argument's (undefined) slot
         if (need_ro) out[0] = g_ro;
@@ -404,13 +421,13 @@ std::vector<Tensor> render(const Config& cfg, const Tensor& rays_o, const Tensor
                            const std::vector<Tensor>& planes, const std::vector<Tensor>& params, const Tensor& t_free, const Tensor& t_surf,
                            const Tensor& rng_state, uint64_t seed, int64_t ray_offset, const c10::optional<Tensor>& gt_color,
                            const c10::optional<Tensor>& ray_mask, const c10::optional<Tensor>& scratch, const c10::optional<Tensor>& acc_out,
-                           const std::vector<double>& weights5, bool relayout) {
+                           const std::vector<double>& weights5, bool relayout, bool saved_hidden) {
     TORCH_CHECK(cfg.n_strat >= 3 && cfg.bound_sample.size() == 6 && cfg.bound_decode.size() == 6, "Config not initialised");
     TORCH_CHECK(planes.size() == 12 && params.size() == 12, "expected 12 planes and 12 decoder tensors");
     RenderNode::IO io;
     io.cfg = cfg;
     io.gt_depth = gt_depth; io.t_free = t_free; io.t_surf = t_surf; io.rng_state = rng_state;
-    io.seed = seed; io.ray_offset = ray_offset; io.relayout = relayout;
+    io.seed = seed; io.ray_offset = ray_offset; io.relayout = relayout; io.saved_hidden = saved_hidden;
     TORCH_CHECK(t_free.numel() == cfg.n_strat && t_surf.numel() == cfg.n_imp && rng_state.scalar_type() == at::kInt, "bad sampler tensors");
     if (gt_color.has_value()) {
         TORCH_CHECK(scratch.has_value() && weights5.size() == 5, "the fused loss needs its scratch and 5 weights");
@@ -449,8 +466,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("render", &render, py::arg("cfg"), py::arg("rays_o"), py::arg("rays_d"), py::arg("gt_depth"), py::arg("beta"), py::arg("planes"),
           py::arg("params"), py::arg("t_free"), py::arg("t_surf"), py::arg("rng_state"), py::arg("seed"), py::arg("ray_offset"),
           py::arg("gt_color") = py::none(), py::arg("ray_mask") = py::none(), py::arg("scratch") = py::none(), py::arg("acc_out") = py::none(),
-          py::arg("weights5") = std::vector<double>(), py::arg("relayout") = false);
+          py::arg("weights5") = std::vector<double>(), py::arg("relayout") = false, py::arg("saved_hidden") = true);
     m.def("mapping_loss", &mapping_loss, py::arg("depth"), py::arg("rgb"), py::arg("sdf"), py::arg("z_vals"), py::arg("gt_depth"),
           py::arg("gt_color"), py::arg("truncation"), py::arg("weights5"), py::arg("ray_mask"), py::arg("scratch"));
     m.def("abi_version", []() { return eslam_abi_version(); });
+    m.def("require_saved_hidden", [](const c10::optional<Tensor>& h, int64_t R, int64_t S) {
+        require_saved_hidden(h.has_value() ? *h : Tensor(), R, S);
+    }, py::arg("hidden"), py::arg("R"), py::arg("S"), "the check RenderNode's backward makes on its saved hidden layer before its first launch");
 }

@@ -289,6 +289,53 @@ def ray_order_async(rays_o, rays_d, grad_planes=None):
 
 _fused_loss = None
 
+# A float32 render call that will be back-propagated also saves the decoders' first hidden layer (128 bytes per sample beside
+# the 512 of the features), and its backward reads it instead of rebuilding it from the features: same bits, 16 of the
+# decoder backward's 52 MFMAs per 16 samples less.  The renderer's saved_hidden keyword (a plain argument all the way down to
+# RenderFn.apply and the compiled render()) gives a call the recompute kernels; the mixed-precision and free-point paths never
+# save it.  `with ops.saved_hidden(False):` changes what a call WITHOUT the keyword does - a process-wide default, for code
+# that cannot reach the call (not for threads that want different settings: pass the keyword there).
+SAVED_HIDDEN_DEFAULT = True
+_saved_hidden = None
+
+
+class saved_hidden:
+    """Context manager: the default of render calls inside that give no saved_hidden keyword; None = SAVED_HIDDEN_DEFAULT."""
+
+    def __init__(self, on):
+        self.on = None if on is None else bool(on)
+
+    def __enter__(self):
+        global _saved_hidden
+        self.prev, _saved_hidden = _saved_hidden, self.on
+        return self
+
+    def __exit__(self, *exc):
+        global _saved_hidden
+        _saved_hidden = self.prev
+        return False
+
+
+def saved_hidden_on():
+    return SAVED_HIDDEN_DEFAULT if _saved_hidden is None else _saved_hidden
+
+
+def saved_hidden_floats(R, S):
+    """Floats of the saved first hidden layer of an [R, S] render call: 2 * R * ceil(S / 16) * 256."""
+    return int(_hip.lib().eslam_saved_hidden_floats(int(R), int(S)))
+
+
+def require_saved_hidden(hid, R, S):
+    """The backward of a call that saved its hidden layer: refuse a missing or short buffer before anything is launched."""
+    want = saved_hidden_floats(R, S)
+    if hid is None:
+        raise RuntimeError(f"saved hidden layer: the forward pass left no buffer ({want} floats for {R} x {S} samples expected)")
+    if hid.dtype != torch.float32 or not hid.is_contiguous() or hid.numel() < want:
+        raise RuntimeError(f"saved hidden layer: {hid.numel()} {hid.dtype} elements, {want} contiguous float32 needed for "
+                           f"{R} x {S} samples")
+    return hid
+
+
 # The compiled host glue of a render call (myslam_amd/csrc/eslam_torch_ext.cpp, `make torch_ext`): optional - the Python code below
 # is the general path and does the same through ctypes.  ESLAM_TORCH_EXT=0 switches it off.
 _EXT_WANTED = os.environ.get("ESLAM_TORCH_EXT", "1") != "0"
@@ -320,7 +367,7 @@ def ext_render_ok(rays_o, n_strat, rand):
             _rng_override is None and rays_o.is_cuda and torch_ext() is not None)
 
 
-def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_strat, n_imp, fl, relayout=False):
+def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_strat, n_imp, fl, relayout=False, saved_hidden=None):
     """One compiled call: [planes -> channels-last scratch when `relayout`,] ray order + gradient clear (side stream), sampler,
     forward (+ the loss's sums), join.  fl: the active ops.fused_loss context or None.  Returns depth, rgb, sdf, z_vals."""
     dev = rays_o.device
@@ -330,17 +377,18 @@ def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_s
         state[0] += 1                  # samples drawn earlier were never rendered
         _rng_pending[dev.index] = False
     ext = torch_ext()
+    keep_h = saved_hidden_on() if saved_hidden is None else bool(saved_hidden)
     with _hip.on_device(dev):
         if fl is None:
             outs = ext.render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, linspace01(n_strat, dev), linspace01(n_imp, dev),
-                              state, seed_v, _ray_offset, relayout=relayout)
+                              state, seed_v, _ray_offset, relayout=relayout, saved_hidden=keep_h)
         else:
             mask = fl.ray_mask
             if mask is not None:
                 mask = _c(mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8))
             outs = ext.render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, linspace01(n_strat, dev), linspace01(n_imp, dev),
                               state, seed_v, _ray_offset, fl.gt_color, mask, _loss_scratch(dev, rays_o.shape[0]), fl.acc_out,
-                              list(fl.state.weights5), relayout)
+                              list(fl.state.weights5), relayout, keep_h)
             fl.loss, fl.acc = outs[4], outs[5]
             fl.value = outs[4].detach()
     return outs[0], outs[1], outs[2], outs[3]
@@ -578,7 +626,9 @@ def _take_rng_bump(dev):
 
 class RenderFn(torch.autograd.Function):
     """depth, rgb, sdf[, loss] = RenderFn.apply(rays_o, rays_d, z_vals, bound6, beta, order, lossctx, *12 planes,
-                                                *12 decoder params)
+                                                *12 decoder params[, saved_hidden])
+    saved_hidden (optional, a bool behind the 24 tensors): whether a float32 call that will be back-propagated saves the
+    decoders' first hidden layer for its backward; not given = ops.saved_hidden_on().
 
     Forward = eslam_render_fwd, backward = eslam_render_bwd (reference: Renderer.py:136-147 and its autograd).
     order = (perm, stream) from ray_order_async, or None.
@@ -611,6 +661,11 @@ class RenderFn(torch.autograd.Function):
         raw_rgb = torch.empty(R, S, 3, device=dev) if needs else None
         # saved features: float32, or (mixed precision) the bf16 values the decoders consumed - half the bytes
         feat = torch.empty(R * S, 128, device=dev, dtype=torch.float32 if half is None else torch.bfloat16) if needs else None
+        # the first hidden layer of both decoders as the forward kernel holds it (float32 planes): the backward reads it back
+        ctx.extra_inputs = len(tensors) - 24
+        keep_h = bool(tensors[24]) if ctx.extra_inputs else saved_hidden_on()
+        ctx.saved_hidden = bool(needs and half is None and R > 0 and keep_h)
+        hid = torch.empty(saved_hidden_floats(R, S), device=dev) if ctx.saved_hidden else None
         order = None
         ctx.pregrads = None
         if order_in is not None:
@@ -625,11 +680,11 @@ class RenderFn(torch.autograd.Function):
         ctx.lossctx = None
         with _hip.on_device(dev):
             if fl is None:
-                _hip.check(lib.eslam_render_fwd(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(rays_o),
-                                                _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(depth), _hip.ptr(rgb),
-                                                _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat),
-                                                None, _take_rng_bump(dev),
-                                                _hip.stream_handle(dev)), "eslam_render_fwd")
+                _hip.check(lib.eslam_render_fwd_h(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(rays_o),
+                                                  _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(depth), _hip.ptr(rgb),
+                                                  _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat),
+                                                  None, _take_rng_bump(dev), _hip.ptr(hid),
+                                                  _hip.stream_handle(dev)), "eslam_render_fwd")
             else:
                 _hip.require_gpu_f32("gt_depth", fl.gt_depth)
                 _hip.require_gpu_f32("gt_color", fl.gt_color)
@@ -641,14 +696,15 @@ class RenderFn(torch.autograd.Function):
                 st = fl.state
                 st.gt_depth, st.gt_color, st.ray_mask, st.acc, st.value = _c(fl.gt_depth), _c(fl.gt_color), mask, fl.acc, fl.value
                 w5 = (ctypes.c_float * 5)(*st.weights5)
-                _hip.check(lib.eslam_render_fwd_loss(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(rays_o),
-                                                     _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(depth),
-                                                     _hip.ptr(rgb), _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat),
-                                                     None,
-                                                     _hip.ptr(st.gt_depth), _hip.ptr(st.gt_color),
-                                                     st.truncation, w5, _hip.ptr(mask),
-                                                     _hip.ptr(_loss_scratch(dev, R)), _hip.ptr(fl.acc), _hip.ptr(fl.value),
-                                                     _take_rng_bump(dev), _hip.stream_handle(dev)), "eslam_render_fwd_loss")
+                _hip.check(lib.eslam_render_fwd_loss_h(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(rays_o),
+                                                       _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(depth),
+                                                       _hip.ptr(rgb), _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat),
+                                                       None,
+                                                       _hip.ptr(st.gt_depth), _hip.ptr(st.gt_color),
+                                                       st.truncation, w5, _hip.ptr(mask),
+                                                       _hip.ptr(_loss_scratch(dev, R)), _hip.ptr(fl.acc), _hip.ptr(fl.value),
+                                                       _take_rng_bump(dev), _hip.ptr(hid), _hip.stream_handle(dev)),
+                           "eslam_render_fwd_loss")
                 ctx.lossctx = st
         if order_in is not None and side is not None:
             # join the side stream (ray order, gradient clear) BEHIND the forward kernel: the work beside it has overlapped,
@@ -657,7 +713,8 @@ class RenderFn(torch.autograd.Function):
         if needs:
             ctx.bound6 = bound6
             ctx.order_stream = None
-            ctx.save_for_backward(rays_o, rays_d, z_vals, sdf, raw_rgb, feat, order, beta, depth, rgb, *planes, *params)
+            ctx.save_for_backward(rays_o, rays_d, z_vals, sdf, raw_rgb, feat, order, beta, depth, rgb, *planes, *params,
+                                  *(() if hid is None else (hid,)))
         if fl is not None:
             return depth, rgb, sdf, fl.value.detach()     # an alias: the state must not hold the output object itself
         return depth, rgb, sdf
@@ -668,6 +725,9 @@ class RenderFn(torch.autograd.Function):
         rays_o, rays_d, z_vals, sdf, raw_rgb, feat, order, beta, depth, rgb = saved[:10]
         planes, params = saved[10:22], saved[22:34]
         R, S = z_vals.shape
+        hid = None
+        if ctx.saved_hidden:
+            hid = require_saved_hidden(saved[34] if len(saved) > 34 else None, R, S)
         dev = rays_o.device
         lib = _hip.lib()
         if getattr(ctx, "order_stream", None) is not None:
@@ -714,27 +774,28 @@ class RenderFn(torch.autograd.Function):
                 # has put the global ones into acc_global by now)
                 up = _c(g_loss.detach().reshape(1).to(torch.float32))
                 w5 = (ctypes.c_float * 5)(*fl.weights5)
-                _hip.check(lib.eslam_render_bwd_loss(
+                _hip.check(lib.eslam_render_bwd_loss_h(
                     arr, ctypes.byref(dec), _hip.make_bound(ctx.bound6), _hip.ptr(rays_o), _hip.ptr(rays_d),
                     _hip.ptr(z_vals), R, S, _hip.ptr(sdf), _hip.ptr(raw_rgb), _hip.ptr(feat), _hip.ptr(depth), _hip.ptr(rgb),
                     _hip.ptr(fl.gt_depth), _hip.ptr(fl.gt_color), fl.truncation, w5, _hip.ptr(fl.ray_mask),
                     _hip.ptr(fl.acc if fl.acc_global is None else fl.acc_global), _hip.ptr(up), _hip.ptr(fl.value) if fl.rewrite_value else None, _hip.ptr(g_depth),
                     _hip.ptr(g_rgb), _hip.ptr(g_sdf), _hip.ptr(g_dec), _hip.ptr(g_beta), _hip.ptr(g_ro), _hip.ptr(g_rd),
-                    _hip.ptr(order), _hip.ptr(ws), _hip.stream_handle(dev)), "eslam_render_bwd_loss")
+                    _hip.ptr(order), _hip.ptr(ws), _hip.ptr(hid), _hip.stream_handle(dev)), "eslam_render_bwd_loss")
             else:
-                _hip.check(lib.eslam_render_bwd(arr, ctypes.byref(dec), _hip.make_bound(ctx.bound6), _hip.ptr(rays_o),
-                                                _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(sdf), _hip.ptr(raw_rgb),
-                                                _hip.ptr(feat), _hip.ptr(g_depth), _hip.ptr(g_rgb), _hip.ptr(g_sdf),
-                                                _hip.ptr(g_dec), _hip.ptr(g_beta), _hip.ptr(g_ro), _hip.ptr(g_rd),
-                                                _hip.ptr(order), _hip.ptr(ws), _hip.stream_handle(dev)),
+                _hip.check(lib.eslam_render_bwd_h(arr, ctypes.byref(dec), _hip.make_bound(ctx.bound6), _hip.ptr(rays_o),
+                                                  _hip.ptr(rays_d), _hip.ptr(z_vals), R, S, _hip.ptr(sdf), _hip.ptr(raw_rgb),
+                                                  _hip.ptr(feat), _hip.ptr(g_depth), _hip.ptr(g_rgb), _hip.ptr(g_sdf),
+                                                  _hip.ptr(g_dec), _hip.ptr(g_beta), _hip.ptr(g_ro), _hip.ptr(g_rd),
+                                                  _hip.ptr(order), _hip.ptr(ws), _hip.ptr(hid), _hip.stream_handle(dev)),
                            "eslam_render_bwd")
         if sink is not None:
             # the data-parallel caller owns .grad assignment (FlatGrads.assign): hand autograd nothing to accumulate
-            return (g_ro if need[0] else None, g_rd if need[1] else None) + (None,) * (L - 2 + 24)
+            return (g_ro if need[0] else None, g_rd if need[1] else None) + (None,) * (L - 2 + 24 + ctx.extra_inputs)
         dec_grads = _split_dec_grads(g_dec) if g_dec is not None else [None] * 12
         out = [g_ro if need[0] else None, g_rd if need[1] else None, None, None, g_beta if need[4] else None, None, None]
         out += [grads[i] if (need_planes and need[L + i]) else None for i in range(12)]
         out += [dec_grads[i] if need[L + 12 + i] else None for i in range(12)]
+        out += [None] * ctx.extra_inputs
         return tuple(out)
 
 

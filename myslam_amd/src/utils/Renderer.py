@@ -20,9 +20,13 @@ class Renderer(object):
         self.bound = eslam.bound.to(eslam.device, non_blocking=True)
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = eslam.H, eslam.W, eslam.fx, eslam.fy, eslam.cx, eslam.cy
 
-    def render_batch_ray(self, all_planes, decoders, rays_d, rays_o, device, truncation, gt_depth=None, _rand=None):
+    def render_batch_ray(self, all_planes, decoders, rays_d, rays_o, device, truncation, gt_depth=None, _rand=None,
+                         saved_hidden=None):
         """Renderer.py:63-147.  NB argument order (rays_d, rays_o).  Returns depth [R], rgb [R,3], sdf [R,S],
-        z_vals [R,S].  `_rand` (tests only) injects the three uniform tensors instead of drawing them."""
+        z_vals [R,S].  `_rand` (tests only) injects the three uniform tensors instead of drawing them.
+        saved_hidden: True / False = the backward of this call reads the first hidden layer the forward saved / recomputes it
+        (same bits either way); None = ops.saved_hidden_on().  Handed down as a plain argument."""
+        keep_h = ops.saved_hidden_on() if saved_hidden is None else bool(saved_hidden)
         n_rays = rays_o.shape[0]
         S = self.n_stratified + self.n_importance
         if gt_depth is None:
@@ -36,7 +40,7 @@ class Renderer(object):
             # the common case as ONE compiled call (eslam_torch_ext.cpp); everything below is the same sequence through ctypes
             return ops.ext_render(self._ext_cfg(truncation, decoders), rays_o, rays_d, gt_depth, beta,
                                   [p for grp in all_planes for p in grp], ops.decoder_params(decoders), self.n_stratified,
-                                  self.n_importance, ops.current_fused_loss(), ops.wants_relayout(all_planes, n_rays * S))
+                                  self.n_importance, ops.current_fused_loss(), ops.wants_relayout(all_planes, n_rays * S), keep_h)
         # planes in the reference's NCHW layout: per-call channels-last scratch copies (gradients flow back through them)
         all_planes = ops.planes_for_kernels(all_planes, n_rays * S)
         flat_planes = [p for grp in all_planes for p in grp]
@@ -55,7 +59,7 @@ class Renderer(object):
         bound6 = ops.bound_to_host(decoders.bound)
         fl = ops.current_fused_loss()          # set by render_batch_ray_with_loss
         outs = ops.RenderFn.apply(rays_o, rays_d, z_vals, bound6, beta, order, fl, *flat_planes,
-                                  *ops.decoder_params(decoders))
+                                  *ops.decoder_params(decoders), keep_h)
         if fl is not None:
             fl.loss = outs[3]
         return outs[0], outs[1], outs[2], z_vals
@@ -79,13 +83,13 @@ class Renderer(object):
         return d
 
     def render_batch_ray_with_loss(self, all_planes, decoders, rays_d, rays_o, device, truncation, gt_depth, gt_color,
-                                   weights, ray_mask=None, _rand=None, acc_out=None):
+                                   weights, ray_mask=None, _rand=None, acc_out=None, saved_hidden=None):
         """render_batch_ray + the mapping loss (src/Mapper.py:337-346): its sums are formed in the forward kernel's
         epilogue and its gradients inside the backward kernel.  Returns (depth, rgb, sdf, z_vals, pre); pre.loss is the
         loss (losses.mapping_loss(..., precomputed=pre) returns it): call .backward() on it."""
         with ops.fused_loss(gt_depth, gt_color, truncation, weights, ray_mask, acc_out=acc_out) as pre:
             depth, rgb, sdf, z_vals = self.render_batch_ray(all_planes, decoders, rays_d, rays_o, device, truncation,
-                                                            gt_depth=gt_depth, _rand=_rand)
+                                                            gt_depth=gt_depth, _rand=_rand, saved_hidden=saved_hidden)
         return depth, rgb, sdf, z_vals, pre
 
     def sdf2alpha(self, sdf, beta=10):
