@@ -195,6 +195,14 @@ int eslam_render_fwd_lowp(const eslam_plane_t* planes_f16, const eslam_decoders_
  * rays, so a caller can run it on a side stream next to the samplers.  (ABI 5: perm was [R].)                           */
 int eslam_ray_order(const float* rays_o, const float* rays_d, int R, int32_t* perm, eslam_stream_t stream);
 
+/* eslam_ray_order and the clear of the iteration's plane-gradient buffer as ONE launch (one node of a captured graph instead
+ * of a memset node followed by the order): the ordering workgroups carry the lowest block numbers, the workgroups behind them
+ * zero clear_bytes bytes at clear_ptr with 16-byte stores; the two are independent.  clear_ptr must be 16-byte aligned and
+ * clear_bytes a multiple of 4, else 1 is returned, eslam_last_error() says why and nothing is launched.  clear_ptr = NULL
+ * with clear_bytes = 0 orders only; R = 0 clears only.  (Added under ABI 5.)                                              */
+int eslam_ray_order_clear(const float* rays_o, const float* rays_d, int R, int32_t* perm, void* clear_ptr,
+                          int64_t clear_bytes, eslam_stream_t stream);
+
 /* Bytes of scratch eslam_render_bwd / eslam_decode_bwd need for n_points = R*S points.               */
 int64_t eslam_bwd_workspace_bytes(int64_t n_points);
 

@@ -288,38 +288,31 @@ __global__ __launch_bounds__(256) void sample_z_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------
 // K4: reference src/utils/Renderer.py:108-134 + src/common.py:41-77.  One wave per zero-depth ray.
 // ---------------------------------------------------------------------------------------------------------
-// ONE WORKGROUP PER RAY.  A ray with depth (WITH_DEPTH: the same launch also produces those rows, K3) is one wave's job
-// and the other three leave at once; a depth-less ray is worked on by all four waves: the SDF decode of its n_strat
-// points - a chain of 6 dependent gather + MLP blocks at n_strat = 88 when one wave did it alone, 42 us of this kernel for a
-// 1024-ray ScanNet batch with 10 % depth-less rays - is dealt out block by block, then wave 0 inverts the cdf.
-// (Four rays per workgroup with the four waves taking the workgroup's depth-less rays one after the other was SLOWER, 76 us:
-// the kernel then lasts as long as its unluckiest workgroup, which holds two or three such rays.)
-template <bool CL, bool WITH_DEPTH>
-__global__ __launch_bounds__(256, 2) void importance_z_kernel(const PlaneSet planes, const eslam_decoders_t dec,
-                                                           const Bound bnd, const float* __restrict__ rays_o,
-                                                           const float* __restrict__ rays_d,
-                                                           const float* __restrict__ gt_depth, int R, int n_strat,
-                                                           int n_imp, const float* __restrict__ t_free,
-                                                           const float* __restrict__ t_rand_uni,
-                                                           const float* __restrict__ u_rand,
-                                                           float* __restrict__ z_vals, float c15, float c3,
-                                                           const float* __restrict__ t_surf,
-                                                           const float* __restrict__ t_rand, const RngArg rng_arg) {
-    const Rng rng = make_rng(rng_arg);
-    __shared__ __attribute__((aligned(16))) float wlds[DEC_LDS];          // the SDF decoder only
-    __shared__ float zu[ESLAM_MAX_SAMPLES];      // jittered uniform samples (depth rows: the rank merge's scratch)
-    __shared__ float wt[ESLAM_MAX_SAMPLES];      // uniform samples before the jitter, then weights -> cdf
-    __shared__ float zn[ESLAM_MAX_SAMPLES];      // importance samples
-    __shared__ float al[ESLAM_MAX_SAMPLES];      // alpha of the n_strat points
+// The body of one depth-less ray, run by the four waves of a workgroup: the SDF decode of its n_strat points - a chain of
+// 6 dependent gather + MLP blocks at n_strat = 88 when one wave did it alone, 42 us of this kernel for a 1024-ray ScanNet batch
+// with 10 % depth-less rays - is dealt out block by block, then wave 0 inverts the cdf.  The caller has staged the SDF decoder's
+// weights into wlds (this function's first barrier also covers that staging) and puts a barrier behind the call before the
+// LDS rows are used again.
+struct ImpLds {
+    float* wlds;     // [DEC_LDS] the SDF decoder only
+    float* zu;       // jittered uniform samples
+    float* wt;       // uniform samples before the jitter, then weights -> cdf
+    float* zn;       // importance samples
+    float* al;       // alpha of the n_strat points
+};
+template <bool CL>
+__device__ __forceinline__ void importance_row(const PlaneSet& planes, const eslam_decoders_t& dec, const Bound& bnd,
+                                               const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                               const int ray, const int n_strat, const int n_imp,
+                                               const float* __restrict__ t_free, const float* __restrict__ t_rand_uni,
+                                               const float* __restrict__ u_rand, float* __restrict__ z_vals, const Rng& rng,
+                                               const ImpLds& L) {
+    float* const wlds = L.wlds;
+    float* const zu = L.zu;
+    float* const wt = L.wt;
+    float* const zn = L.zn;
+    float* const al = L.al;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ray = blockIdx.x;
-    const float d0 = gt_depth[ray];
-    if (d0 > 0.0f) {                                 // uniform over the workgroup
-        if (WITH_DEPTH && wave == 0)
-            depth_guided_row(d0, ray, n_strat, n_imp, c15, c3, t_free, t_surf, t_rand, z_vals + (int64_t)ray * (n_strat + n_imp), zu, lane, rng);
-        return;
-    }
-    stage_decoder_weights_one(wlds, dec, 0, threadIdx.x, blockDim.x);
     const int r = lane & 15, q = lane >> 4;                                  // MFMA role (eslam_decode_tile.h)
     const int gp = gather_point<CL>(lane), gq = gather_piece<CL>(lane);     // gather role
     const float beta = dec.beta[0];
@@ -439,6 +432,114 @@ __global__ __launch_bounds__(256, 2) void importance_z_kernel(const PlaneSet pla
             }
         }
         out_row[pos] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// K4 (and, WITH_DEPTH, K3 in the same launch).
+// WITH_DEPTH = false (eslam_importance_z): ONE WORKGROUP PER RAY; a ray with depth is left alone, a depth-less ray is worked on
+// by all four waves (importance_row).
+//   (Four rays per workgroup with the four waves taking the workgroup's depth-less rays one after the other was SLOWER, 76 us:
+//   the kernel then lasts as long as its unluckiest workgroup, which holds two or three such rays.)
+// WITH_DEPTH = true (eslam_sample_z_all*): two roles in one launch, chosen by the block number.
+//   depth-less role, the `seg_wgs` blocks of each segment of IMP_SEG rays, IN FRONT (a depth-less ray is the long job of this
+//     launch - the SDF decode of its n_strat points - and is placed first; behind the row role the sampler alone measured
+//     29.9 us at 8192 x 96 and 18.9 us at 5000 x 56 with 10 % depth-less rays, in front 28.5 and 16.7, one workgroup per ray 33.9
+//     and 18.5): workgroup k of a segment scans the segment's depths (ballots + a prefix count, no communication between
+//     workgroups), takes the k-th, (k + seg_wgs)-th, ... ray for which gt_depth > 0 is false, stages the decoder's weights once
+//     and runs importance_row for each of them.  A batch without such rays costs the role one scan and an exit.
+//   row role, the last row_wgs = ceil(R / 4) blocks: wave w of block b writes the depth-guided row of ray 4 b + w when that ray
+//     has depth (the four LDS rows are the four waves' scratch); one workgroup per ray left three of four waves idle.
+// ---------------------------------------------------------------------------------------------------------
+// (Segments of 8192 rays had every workgroup of the role read the whole batch's depths: 1024 workgroups x 16 KB at 4096 rays,
+// and the sampler of a batch WITHOUT depth-less rays took 12.5 us where one workgroup per ray had taken 7.8.  With 1024 rays a
+// thread loads four depths.  The price: rays are dealt out evenly inside a segment only, which is even enough for rays drawn
+// from random pixels of an image.)
+#define IMP_SEG 1024
+template <bool CL, bool WITH_DEPTH>
+__global__ __launch_bounds__(256, WITH_DEPTH ? 4 : 2) void importance_z_kernel(const PlaneSet planes, const eslam_decoders_t dec,
+                                                           const Bound bnd, const float* __restrict__ rays_o,
+                                                           const float* __restrict__ rays_d,
+                                                           const float* __restrict__ gt_depth, int R, int n_strat,
+                                                           int n_imp, const float* __restrict__ t_free,
+                                                           const float* __restrict__ t_rand_uni,
+                                                           const float* __restrict__ u_rand,
+                                                           float* __restrict__ z_vals, float c15, float c3,
+                                                           const float* __restrict__ t_surf,
+                                                           const float* __restrict__ t_rand, const RngArg rng_arg,
+                                                           const int row_wgs, const int seg_wgs) {
+    const Rng rng = make_rng(rng_arg);
+    __shared__ __attribute__((aligned(16))) float wlds[DEC_LDS];
+    __shared__ float zu[ESLAM_MAX_SAMPLES];
+    __shared__ float wt[ESLAM_MAX_SAMPLES];
+    __shared__ float zn[ESLAM_MAX_SAMPLES];
+    __shared__ float al[ESLAM_MAX_SAMPLES];
+    const ImpLds L = {wlds, zu, wt, zn, al};
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (!WITH_DEPTH) {
+        const int ray = blockIdx.x;
+        if (gt_depth[ray] > 0.0f) return;            // uniform over the workgroup
+        stage_decoder_weights_one(wlds, dec, 0, threadIdx.x, blockDim.x);
+        importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, t_rand_uni, u_rand, z_vals, rng, L);
+        return;
+    }
+    const int less_wgs = (int)gridDim.x - row_wgs;
+    if ((int)blockIdx.x >= less_wgs) {
+        const int ray = 4 * ((int)blockIdx.x - less_wgs) + wave;
+        if (ray >= R) return;
+        const float d0 = gt_depth[ray];
+        if (!(d0 > 0.0f)) return;                    // the depth-less role's
+        float* const zs = wave == 0 ? zu : wave == 1 ? wt : wave == 2 ? zn : al;
+        depth_guided_row(d0, ray, n_strat, n_imp, c15, c3, t_free, t_surf, t_rand, z_vals + (int64_t)ray * (n_strat + n_imp), zs, lane, rng);
+        return;
+    }
+    // depth-less role (blocks [0, less_wgs))
+    constexpr int NW = IMP_SEG / 64;                 // 64-ray ballot words of a segment
+    __shared__ unsigned long long less_bits[NW];     // bit i of word w: ray 64 w + i of the segment is depth-less
+    __shared__ unsigned less_before[NW + 1];         // depth-less rays in front of word w; [NW]: of the segment
+    const int j = (int)blockIdx.x;
+    const int seg = j / seg_wgs, k = j - seg * seg_wgs;
+    const int seg_base = seg * IMP_SEG;
+    const int seg_n = min(IMP_SEG, R - seg_base);
+    if (seg_n <= 0 || k >= seg_n) return;            // (uniform) at most one workgroup per ray
+    // wave `wave` forms words wave, wave + 4, ...: all of a thread's loads are issued before the first ballot needs one (a
+    // load per trip of a rolled loop is a dependent L2 latency per trip)
+    float dv[NW / 4];
+#pragma unroll
+    for (int m = 0; m < NW / 4; ++m) {
+        const int i = 64 * (wave + 4 * m) + lane;
+        dv[m] = i < seg_n ? gt_depth[seg_base + i] : 1.0f;
+    }
+#pragma unroll
+    for (int m = 0; m < NW / 4; ++m) {
+        const unsigned long long b = __ballot(!(dv[m] > 0.0f));
+        if (lane == 0) less_bits[wave + 4 * m] = b;
+    }
+    __syncthreads();
+    if (wave == 0) {                                 // one word per lane
+        static_assert(NW <= 64 && NW % 4 == 0, "one ballot word per lane, the same number of words per wave");
+        const unsigned c = lane < NW ? (unsigned)__popcll(less_bits[lane]) : 0u;
+        const unsigned incl = wave_incl_sum_u(c);
+        if (lane < NW) less_before[lane] = incl - c;
+        if (lane == NW - 1) less_before[NW] = incl;
+    }
+    __syncthreads();
+    const int total = (int)less_before[NW];          // <= seg_n <= R
+    if (k >= total) return;                          // (uniform) nothing for this workgroup: one scan and an exit
+    stage_decoder_weights_one(wlds, dec, 0, threadIdx.x, blockDim.x);
+#pragma unroll 1
+    for (int idx = k; idx < total; idx += seg_wgs) {
+        // the word that holds the idx-th depth-less ray: the last w with less_before[w] <= idx (bisection over the NW words)
+        int lo = 0, hi = NW - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if ((int)less_before[mid] <= idx) lo = mid; else hi = mid - 1;
+        }
+        unsigned long long bits = less_bits[lo];
+        for (int skip = idx - (int)less_before[lo]; skip > 0; --skip) bits &= bits - 1ull;       // < 64 trips
+        const int ray = seg_base + 64 * lo + (int)__builtin_ctzll(bits);
+        importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, t_rand_uni, u_rand, z_vals, rng, L);
+        __syncthreads();                             // the rows are free for the next ray
     }
 }
 
@@ -667,11 +768,11 @@ extern "C" int eslam_importance_z(const eslam_plane_t* planes, const eslam_decod
     if (eslam_planes_channels_last(planes, 0, 6))
         hipLaunchKernelGGL((importance_z_kernel<true, false>), grid, block, 0, (hipStream_t)stream, ps, *dec, bnd, rays_o,
                            rays_d, gt_depth, R, n_strat, n_imp, t_free, t_rand_uni, u, z_vals, 0.0f, 0.0f,
-                           (const float*)nullptr, (const float*)nullptr, RngArg{});
+                           (const float*)nullptr, (const float*)nullptr, RngArg{}, 0, 0);
     else
         hipLaunchKernelGGL((importance_z_kernel<false, false>), grid, block, 0, (hipStream_t)stream, ps, *dec, bnd, rays_o,
                            rays_d, gt_depth, R, n_strat, n_imp, t_free, t_rand_uni, u, z_vals, 0.0f, 0.0f,
-                           (const float*)nullptr, (const float*)nullptr, RngArg{});
+                           (const float*)nullptr, (const float*)nullptr, RngArg{}, 0, 0);
     eslam_prof_end(PROF_IMPORTANCE_Z, (hipStream_t)stream);
     return eslam_check_launch("importance_z_kernel");
 }
@@ -701,14 +802,33 @@ static int sample_z_all_impl(const char* who, const eslam_plane_t* planes, const
     const Bound bnd = make_bound(bound6_host);
     const float c15 = (float)(1.5 * truncation);       // as eslam_sample_z
     const float c3 = (float)(3.0 * truncation);
-    dim3 grid(R), block(256);            // one workgroup per ray
+    // row role: four rays with depth per workgroup; depth-less role: per segment of IMP_SEG rays, the workgroups the chip holds
+    // at once (four per CU: the kernel is built for four waves per SIMD) shared among the segments, at most one per ray of a
+    // (full) segment
+    static const int resident = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return 4 * (cus > 0 ? cus : 256);
+    }();
+    const int row_wgs = (R + 3) / 4;
+    const int nseg = (R + IMP_SEG - 1) / IMP_SEG;
+    int seg_wgs = resident / nseg;
+    if (seg_wgs < 1) seg_wgs = 1;
+    if (seg_wgs > (R < IMP_SEG ? R : IMP_SEG)) seg_wgs = R < IMP_SEG ? R : IMP_SEG;
+    if ((int64_t)row_wgs + (int64_t)nseg * seg_wgs > 0x7FFFFFFF) {
+        eslam_set_error("%s: batch too large", who);
+        return 1;
+    }
+    dim3 grid(row_wgs + nseg * seg_wgs), block(256);
     eslam_prof_begin(PROF_SAMPLE_Z, (hipStream_t)stream);
     if (eslam_planes_channels_last(planes, 0, 6))
         hipLaunchKernelGGL((importance_z_kernel<true, true>), grid, block, 0, (hipStream_t)stream, ps, *dec, bnd, rays_o,
-                           rays_d, gt_depth, R, n_strat, n_imp, t_free, t_rand_uni, u, z_vals, c15, c3, t_surf, t_rand, rng);
+                           rays_d, gt_depth, R, n_strat, n_imp, t_free, t_rand_uni, u, z_vals, c15, c3, t_surf, t_rand, rng,
+                           row_wgs, seg_wgs);
     else
         hipLaunchKernelGGL((importance_z_kernel<false, true>), grid, block, 0, (hipStream_t)stream, ps, *dec, bnd, rays_o,
-                           rays_d, gt_depth, R, n_strat, n_imp, t_free, t_rand_uni, u, z_vals, c15, c3, t_surf, t_rand, rng);
+                           rays_d, gt_depth, R, n_strat, n_imp, t_free, t_rand_uni, u, z_vals, c15, c3, t_surf, t_rand, rng,
+                           row_wgs, seg_wgs);
     eslam_prof_end(PROF_SAMPLE_Z, (hipStream_t)stream);
     return eslam_check_launch("importance_z_kernel<with depth>");
 }

@@ -43,8 +43,8 @@ __device__ __forceinline__ unsigned spread3(unsigned v) {      // 10 bits -> eve
 // key = 15-bit Morton code of the point one metre along the ray, quantised inside the chunk's bounding box of such
 // points (rays of one camera: a patch of the unit sphere round its centre; several cameras: several patches, and
 // rays of nearby cameras with similar directions end up adjacent, which is what shares texels).  Order inside a cell
-// is arbitrary (atomic tickets).  perm[chunk*SORT_MAX + i] = ray id.  ~5 us for 4096 rays (a 78-stage bitonic
-// network in one workgroup took 62 us).
+// is arbitrary (atomic tickets).  perm[chunk*SORT_MAX + i] = ray id.  (A 78-stage bitonic network in one workgroup took
+// 62 us for 4096 rays; this kernel's time is in DESIGN.md section 5.)
 // When all rays of the chunk leave from ONE point (a tracking batch; a mapping batch of a single frame) their
 // directions form a 2-D patch, and a 3-D Morton code wastes a third of its bits on a coordinate the other two
 // determine: the key is then the azimuth of the direction projected into the order's plane (see below).  Round 2's
@@ -55,10 +55,26 @@ __device__ __forceinline__ unsigned spread3(unsigned v) {      // 10 bits -> eve
 #define ORD_PER_THREAD (SORT_MAX / 1024)
 // key_bits (12 or 14): keys of the counting sort.  The histogram's zero fill and scan are what this single-workgroup
 // kernel spends its time on, so small batches get short keys (12 bits for <= 1024 rays: 2048 words instead of 8192).
+// One launch, two independent roles chosen by the block number: blocks [0, n_order = chunks * ESLAM_RAY_ORDERS) order the rays
+// (block b: chunk b / ESLAM_RAY_ORDERS, orientation b % ESLAM_RAY_ORDERS - the lowest numbers, so that they are placed first: they
+// are the long ones), the blocks behind them zero clear_words floats at `clear` (16-byte aligned; the iteration's plane-gradient
+// buffer) with 16-byte stores.  A replayed hipGraph pays ~3 us per node whatever its size (shard_prologue_kernel), and a memset
+// node in front of the order held the order back by the memset's whole length.
 __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict__ rays_o,
                                                          const float* __restrict__ rays_d, int R,
-                                                         int* __restrict__ perm, int key_bits) {
+                                                         int* __restrict__ perm, int key_bits, const int n_order,
+                                                         float* __restrict__ clear, const long long clear_words) {
     extern __shared__ __attribute__((aligned(16))) unsigned hist[];       // [(1 << key_bits) / 2] packed 16-bit counters
+    if ((int)blockIdx.x >= n_order) {
+        const long long n16 = clear_words >> 2;
+        const long long stride = (long long)(gridDim.x - n_order) * 1024;
+        float4_t* const c4 = (float4_t*)clear;
+        const float4_t z4 = {0.f, 0.f, 0.f, 0.f};
+        for (long long i = (long long)((int)blockIdx.x - n_order) * 1024 + threadIdx.x; i < n16; i += stride) c4[i] = z4;
+        if ((int)blockIdx.x == n_order && (long long)threadIdx.x < (clear_words & 3)) clear[4 * n16 + threadIdx.x] = 0.f;
+        return;
+    }
+    const int chunk = (int)blockIdx.x / ESLAM_RAY_ORDERS;
     const int nwords = (1 << key_bits) >> 1;
     const int mbits = key_bits / 3;                                       // Morton grid: 2^mbits per axis
     __shared__ float red[16][6];
@@ -76,45 +92,85 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
     if (tid < SORT_MAX / 64) cam_bits[tid] = 0ull;
     if (tid < NCAM_MAX) { cam_dir[tid][0] = cam_dir[tid][1] = cam_dir[tid][2] = 0.f; cam_ext[tid][0] = 0xFFFFFFFFu; cam_ext[tid][1] = 0u; }
     __syncthreads();
-    const int base = blockIdx.x * SORT_MAX;
+    const int base = chunk * SORT_MAX;
     const int n = min(SORT_MAX, R - base);
     // blockIdx.y = plane orientation (0: xy, 1: xz, 2: yz): order number o is written to perm + o * R.  When the rays share one
     // origin, order o sorts them by the AZIMUTH of their direction projected into plane o: the rays of a bundle then lie on top
     // of each other in that plane's projection whatever their angle out of it, and that is what shares cells - a plane collapses
     // one axis, so a square patch of the image (round 2's Hilbert order: one order for all planes) spreads over many more cells of
     // each plane than a thin wedge does.  tools/sim_order.py, bench rays: 58.8 k cell flushes against 135 k.
-    const int orient = blockIdx.y;
+    const int orient = (int)blockIdx.x % ESLAM_RAY_ORDERS;
     float* const fan = (float*)(perm + (size_t)ESLAM_RAY_ORDERS * R);      // [ESLAM_RAY_ORDERS] angular extent of the fan in each plane (0: unknown)
     perm += (size_t)orient * R;
     const int pa = orient == 2 ? 1 : 0, pb = orient == 0 ? 1 : 2;       // the plane's two axes
 
-    // Rays are re-read from memory (98 KB, cache resident) in every pass instead of being held in 24 registers per
-    // thread: at 1024 threads per workgroup the budget is 128 VGPRs, and round 2's Hilbert path spilled.
-    auto unit_dir = [&](int ray, float o[3], float d[3]) {
-        const float dx = rays_d[3 * ray], dy = rays_d[3 * ray + 1], dz = rays_d[3 * ray + 2];
+    // Every thread reads its rays ONCE, four at a time with all of the loads in flight together, and keeps their unit directions'
+    // two components in this order's plane (16 registers) for the single-origin branch below.  The other two branches re-read them from memory (98 KB, cache
+    // resident) through unit_dir instead: at 1024 threads per workgroup the budget is 128 VGPRs, and round 2's Hilbert path spilled.
+    auto normalise = [](float dx, float dy, float dz, float d[3]) {
         const float inv = rsqrtf(fmaxf(dx * dx + dy * dy + dz * dz, 1e-20f));
-        o[0] = rays_o[3 * ray]; o[1] = rays_o[3 * ray + 1]; o[2] = rays_o[3 * ray + 2];
         d[0] = dx * inv; d[1] = dy * inv; d[2] = dz * inv;
+    };
+    auto unit_dir = [&](int ray, float o[3], float d[3]) {
+        normalise(rays_d[3 * ray], rays_d[3 * ray + 1], rays_d[3 * ray + 2], d);
+        o[0] = rays_o[3 * ray]; o[1] = rays_o[3 * ray + 1]; o[2] = rays_o[3 * ray + 2];
     };
     float lo[3] = {3.4e38f, 3.4e38f, 3.4e38f}, hi[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
     float olo[3] = {3.4e38f, 3.4e38f, 3.4e38f}, ohi[3] = {-3.4e38f, -3.4e38f, -3.4e38f}, dsum[3] = {0.f, 0.f, 0.f};
-    for (int i = tid; i < n; i += 1024) {
-        float o[3], d[3];
-        unit_dir(base + i, o, d);
+    float ua[ORD_PER_THREAD], ub[ORD_PER_THREAD];           // components pa, pb of the unit directions
+    static_assert(ORD_PER_THREAD % 4 == 0, "rays are read four per thread at a time");
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            olo[a] = fminf(olo[a], o[a]); ohi[a] = fmaxf(ohi[a], o[a]);
-            dsum[a] += d[a];
-            const float p = o[a] + d[a];
-            lo[a] = fminf(lo[a], p); hi[a] = fmaxf(hi[a], p);
+    for (int k0 = 0; k0 < ORD_PER_THREAD; k0 += 4) {
+        float ro[4][3], rd[4][3], rp[4][3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) ro[k][a] = rd[k][a] = rp[k][a] = 0.f;
+            ua[k0 + k] = ub[k0 + k] = 0.f;
         }
-        bool first = i == 0;
-        if (!first) {
-            const float* po = rays_o + 3 * (size_t)(base + i - 1);
-            first = po[0] != o[0] || po[1] != o[1] || po[2] != o[2];
+        if (k0 * 1024 >= n) continue;                         // (uniform over the workgroup)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = tid + (k0 + k) * 1024;
+            if (i < n) {
+                const float* po = rays_o + 3 * (size_t)(base + i);
+                const float* pd = rays_d + 3 * (size_t)(base + i);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { ro[k][a] = po[a]; rd[k][a] = pd[a]; }
+                // the ray in front (which rays start a new camera): the neighbouring lane's, read from memory by lane 0 only
+                if (lane == 0 && i > 0) {
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) rp[k][a] = po[a - 3];
+                }
+            }
         }
-        const unsigned long long fb = __ballot(first);          // (a wave's rays of one trip are 64 consecutive ones)
-        if (lane == 0) cam_bits[i >> 6] = fb;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = tid + (k0 + k) * 1024;
+            float prev[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {                     // (outside the branch: every lane of the wave takes part)
+                const float up = __shfl_up(ro[k][a], 1, WAVE);
+                prev[a] = lane == 0 ? rp[k][a] : up;
+            }
+            if (i < n) {
+                float d[3];
+                normalise(rd[k][0], rd[k][1], rd[k][2], d);
+                const float* o = ro[k];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    olo[a] = fminf(olo[a], o[a]); ohi[a] = fmaxf(ohi[a], o[a]);
+                    dsum[a] += d[a];
+                    const float p = o[a] + d[a];
+                    lo[a] = fminf(lo[a], p); hi[a] = fmaxf(hi[a], p);
+                }
+                ua[k0 + k] = orient == 2 ? d[1] : d[0];
+                ub[k0 + k] = orient == 0 ? d[1] : d[2];
+                const bool first = i == 0 || prev[0] != o[0] || prev[1] != o[1] || prev[2] != o[2];
+                const unsigned long long fb = __ballot(first);          // (a wave's rays of one trip are 64 consecutive ones)
+                if (lane == 0) cam_bits[i >> 6] = fb;
+            }
+        }
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -193,7 +249,7 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
         __syncthreads();
         const int cbits = 32 - __clz(ncam - 1);          // bits for the camera (ncam >= 2)
         const int abits = key_bits - cbits;              // >= 7: key_bits >= 12, cbits <= 5
-        if (tid == 0 && blockIdx.x == 0) fan[orient] = 0.0f;      // several origins: no single fan
+        if (tid == 0 && chunk == 0) fan[orient] = 0.0f;      // several origins: no single fan
 #pragma unroll
         for (int k = 0; k < ORD_PER_THREAD; ++k) {
             const int i = tid + k * 1024;
@@ -211,16 +267,17 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
         }
     } else if (single) {                                // uniform over the workgroup
         const float mpa = mdir[pa] / mlen, mpb = mdir[pb] / mlen;      // the mean direction projected into the plane
-        // the signed angle between the projected direction and the projected mean
-        auto azimuth = [&](int ray) {
-            float o[3], d[3];
-            unit_dir(ray, o, d);
-            return atan2f(mpa * d[pb] - mpb * d[pa], mpa * d[pa] + mpb * d[pb]);
-        };
+        // the signed angle between the projected direction and the projected mean: once per ray, kept for the key pass
+        float az[ORD_PER_THREAD];
         float blo = 3.4e38f, bhi = -3.4e38f;
-        for (int i = tid; i < n; i += 1024) {
-            const float u = azimuth(base + i);
-            blo = fminf(blo, u); bhi = fmaxf(bhi, u);
+#pragma unroll
+        for (int k = 0; k < ORD_PER_THREAD; ++k) {
+            az[k] = 0.f;
+            if (tid + k * 1024 < n) {
+                az[k] = atan2f(mpa * ub[k] - mpb * ua[k], mpa * ua[k] + mpb * ub[k]);
+                blo = fminf(blo, az[k]); bhi = fmaxf(bhi, az[k]);
+            }
+            __builtin_amdgcn_sched_barrier(0);           // one ray at a time keeps the register pressure down
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
@@ -234,19 +291,18 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
         for (int w = 1; w < 16; ++w) { blo = fminf(blo, red2[w][9]); h = fmaxf(h, red2[w][10]); }
         const float sc = (float)(1 << key_bits) / fmaxf(h - blo, 1e-6f);
         // the fan's angular extent in this plane (radians), for the scatter's choice of grid order; the first chunk speaks for the batch
-        if (tid == 0 && blockIdx.x == 0) fan[orient] = h - blo;
+        if (tid == 0 && chunk == 0) fan[orient] = h - blo;
 #pragma unroll
         for (int k = 0; k < ORD_PER_THREAD; ++k) {
             const int i = tid + k * 1024;
             if (i < n) {
-                const unsigned kk = min((unsigned)fmaxf((azimuth(base + i) - blo) * sc, 0.f), (1u << key_bits) - 1u);
+                const unsigned kk = min((unsigned)fmaxf((az[k] - blo) * sc, 0.f), (1u << key_bits) - 1u);
                 key[k] = kk;
                 ticket[k] = (atomicAdd(&hist[kk >> 1], 1u << ((kk & 1u) * 16u)) >> ((kk & 1u) * 16u)) & 0xFFFFu;
             }
-            __builtin_amdgcn_sched_barrier(0);           // one ray at a time keeps the register pressure down
         }
     } else {
-        if (tid == 0 && blockIdx.x == 0) fan[orient] = 0.0f;      // several origins: no fan
+        if (tid == 0 && chunk == 0) fan[orient] = 0.0f;      // several origins: no fan
         float scale[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -820,23 +876,44 @@ __global__ __launch_bounds__(256) void scatter_fixed_to_float_kernel(float* __re
 // ---------------------------------------------------------------------------------------------------------
 int eslam_scatter_v2_init();
 
-// perm [R] <- rays ordered by direction; chunks of SORT_MAX rays are ordered independently
-extern "C" int eslam_ray_order(const float* rays_o, const float* rays_d, int R, int32_t* perm, eslam_stream_t stream) {
-    if (R <= 0) return 0;
-    if (!rays_o || !rays_d || !perm) {
-        eslam_set_error("eslam_ray_order: null argument");
+// perm [R] <- rays ordered by direction; chunks of SORT_MAX rays are ordered independently.  clear / clear_bytes: a buffer the
+// same launch zeroes (NULL / 0: none).
+static int ray_order_launch(const char* who, const float* rays_o, const float* rays_d, int R, int32_t* perm, void* clear,
+                            int64_t clear_bytes, eslam_stream_t stream) {
+    if (clear_bytes < 0 || (clear_bytes > 0 && !clear) || ((uintptr_t)clear & 15) || (clear_bytes & 3)) {
+        eslam_set_error("%s: the buffer to clear must be 16-byte aligned and a multiple of 4 bytes long (%p, %lld bytes)", who, clear,
+                        (long long)clear_bytes);
+        return 1;
+    }
+    if (R <= 0 && clear_bytes == 0) return 0;
+    if (R > 0 && (!rays_o || !rays_d || !perm)) {
+        eslam_set_error("%s: null argument", who);
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
     if (int rc = eslam_scatter_v2_init()) return rc;
-    const int chunks = (R + SORT_MAX - 1) / SORT_MAX;
+    const int chunks = R > 0 ? (R + SORT_MAX - 1) / SORT_MAX : 0;
     const int n = R < SORT_MAX ? R : SORT_MAX;         // rays per chunk
     // (16-bit keys were for the 2-D Hilbert order of round 2: 8 bits per axis.  The azimuth keys are one-dimensional: 14 bits = two
     // bins per ray at 8192 rays, and the histogram's zero fill and scan - 63 us of this kernel at 5000 rays with 16 bits - shrink 4x)
     const int key_bits = n <= 1024 ? 12 : 14;
-    hipLaunchKernelGGL(ray_order_kernel, dim3(chunks, ESLAM_RAY_ORDERS), dim3(1024), ((size_t)1 << key_bits) / 2 * sizeof(unsigned), st,
-                       rays_o, rays_d, R, perm, key_bits);
+    // clearing workgroups: one per 64 KB, at most one per CU of a 256-CU chip (each then stores 16 KB per trip)
+    const int64_t want = (clear_bytes + 65535) / 65536;
+    const int n_clear = (int)(want < 256 ? want : 256);
+    const int n_order = chunks * ESLAM_RAY_ORDERS;
+    hipLaunchKernelGGL(ray_order_kernel, dim3(n_order + n_clear), dim3(1024), ((size_t)1 << key_bits) / 2 * sizeof(unsigned), st,
+                       rays_o, rays_d, R, perm, key_bits, n_order, (float*)clear, (long long)(clear_bytes >> 2));
     return eslam_check_launch("ray_order_kernel");
+}
+
+extern "C" int eslam_ray_order(const float* rays_o, const float* rays_d, int R, int32_t* perm, eslam_stream_t stream) {
+    if (R <= 0) return 0;
+    return ray_order_launch("eslam_ray_order", rays_o, rays_d, R, perm, nullptr, 0, stream);
+}
+
+extern "C" int eslam_ray_order_clear(const float* rays_o, const float* rays_d, int R, int32_t* perm, void* clear_ptr,
+                                     int64_t clear_bytes, eslam_stream_t stream) {
+    return ray_order_launch("eslam_ray_order_clear", rays_o, rays_d, R, perm, clear_ptr, clear_bytes, stream);
 }
 
 // perm: ray order to bundle by (render mode), or NULL for the given order

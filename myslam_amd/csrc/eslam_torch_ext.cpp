@@ -196,8 +196,8 @@ public:
             grad_flat = gv.first;
             grad_views = std::move(gv.second);
             check(eslam_stream_wait(side, st), "eslam_stream_wait");
-            check(eslam_zero_async(grad_flat.data_ptr<float>(), grad_flat.numel() * 4, side), "eslam_zero_async");
-            check(eslam_ray_order(rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), (int)R, perm.data_ptr<int32_t>(), side), "eslam_ray_order");
+            check(eslam_ray_order_clear(rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), (int)R, perm.data_ptr<int32_t>(),
+                                        grad_flat.data_ptr<float>(), grad_flat.numel() * 4, side), "eslam_ray_order_clear");
         }
         if (R > 0) {
             check(eslam_sample_z_all_rng(pd, &dd, io.cfg.bound_sample.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),

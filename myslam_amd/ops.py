@@ -256,7 +256,8 @@ _side_streams = {}
 
 
 def ray_order_async(rays_o, rays_d, grad_planes=None):
-    """Launch eslam_ray_order on a side stream (it depends only on the rays, so it overlaps the samplers).
+    """Launch eslam_ray_order_clear on a side stream (the order depends only on the rays, so it overlaps the samplers; the
+    gradient buffer's clear is a second role of the same launch).
     Returns (perm int32 [3 R + 4]: one order per plane orientation + the fan's extent, stream to join before the order is used[, gradient views]).
     grad_planes: the 12 planes when the coming backward pass will need their gradient buffer: it is allocated here and
     cleared at the HEAD of the side stream, beside the samplers (27 - 70 MB: 6 - 15 us in front of the backward pass
@@ -275,11 +276,11 @@ def ray_order_async(rays_o, rays_d, grad_planes=None):
         pre = _alloc_plane_grads(grad_planes, zero=False)      # on the caller's stream: its allocator's memory
     _hip.stream_wait(dev, side, None)           # the rays - and any earlier use of that memory - come from work on the caller's stream
     with _hip.on_device(dev):
-        if pre is not None:
-            _hip.check(_hip.lib().eslam_zero_async(_hip.ptr(pre[0]), pre[0].numel() * 4, ctypes.c_void_p(side.cuda_stream)),
-                       "eslam_zero_async")
-        _hip.check(_hip.lib().eslam_ray_order(_hip.ptr(ro), _hip.ptr(rd), R, _hip.ptr(perm),
-                                              ctypes.c_void_p(side.cuda_stream)), "eslam_ray_order")
+        # one launch: the order's workgroups in front, the gradient buffer's clear behind them
+        _hip.check(_hip.lib().eslam_ray_order_clear(_hip.ptr(ro), _hip.ptr(rd), R, _hip.ptr(perm),
+                                                    None if pre is None else _hip.ptr(pre[0]),
+                                                    0 if pre is None else pre[0].numel() * 4,
+                                                    ctypes.c_void_p(side.cuda_stream)), "eslam_ray_order_clear")
     perm.record_stream(side)
     for t, src in ((ro, rays_o), (rd, rays_d)):
         if t.data_ptr() != src.data_ptr():
