@@ -203,6 +203,18 @@ int eslam_ray_order(const float* rays_o, const float* rays_d, int R, int32_t* pe
 int eslam_ray_order_clear(const float* rays_o, const float* rays_d, int R, int32_t* perm, void* clear_ptr,
                           int64_t clear_bytes, eslam_stream_t stream);
 
+/* The front of a training step as ONE launch on `stream`: what eslam_ray_order_clear (perm, clear_ptr, clear_bytes) and
+ * eslam_sample_z_all_rng (everything else) do in two, with the same results - z_vals bit for bit; orders with the same keys
+ * (the order inside a key's bin is arbitrary in both).  Nothing is forked to a second stream and nothing has to be joined: the
+ * kernels behind it on `stream` find z_vals, perm and the cleared buffer ready.  The argument checks are those of the two
+ * entries; 1 is returned, eslam_last_error() says why and nothing is launched when one fails.  perm = NULL with
+ * clear_bytes = 0 is eslam_sample_z_all_rng; R = 0 clears only.  (Added under ABI 5.)                                       */
+int eslam_step_front(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                     const float* rays_o, const float* rays_d, const float* gt_depth, int R, int n_strat, int n_imp,
+                     double truncation, const float* t_free, const float* t_surf, int perturb, uint64_t seed,
+                     const uint32_t* rng_state, int64_t ray_offset, float* z_vals, int32_t* perm, void* clear_ptr,
+                     int64_t clear_bytes, eslam_stream_t stream);
+
 /* Bytes of scratch eslam_render_bwd / eslam_decode_bwd need for n_points = R*S points.               */
 int64_t eslam_bwd_workspace_bytes(int64_t n_points);
 

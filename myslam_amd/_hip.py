@@ -94,6 +94,8 @@ SIGNATURES = {
     "eslam_render_fwd_lowp": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "eslam_ray_order": (_i, [_vp, _vp, _i, _vp, _vp]),
     "eslam_ray_order_clear": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "eslam_step_front": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _i, ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp,
+                              _i64, _vp]),
     "eslam_stream_wait": (_i, [_vp, _vp]),
     "eslam_zero_async": (_i, [_vp, _i64, _vp]),
     "eslam_bwd_workspace_bytes": (_i64, [_i64]),

@@ -3,6 +3,7 @@
 // PyTorch launches and 6 host syncs per iteration from the caller's critical path, and to produce z_vals that are
 // bit-identical to the reference's float32 arithmetic (explicitly rounded ops, no FMA contraction).
 #include "eslam_decode_tile.h"
+#include "eslam_ray_order_dev.h"      // (pins its own contraction mode: the ordering role of step_front_kernel)
 
 // hipcc contracts a*b+c into an FMA by default and its __fmul_rn/__fadd_rn are plain operators, so the explicit
 // rounding steps below only survive with contraction switched off for this translation unit's own code.
@@ -293,6 +294,10 @@ __global__ __launch_bounds__(256) void sample_z_kernel(const float* __restrict__
 // with 10 % depth-less rays - is dealt out block by block, then wave 0 inverts the cdf.  The caller has staged the SDF decoder's
 // weights into wlds (this function's first barrier also covers that staging) and puts a barrier behind the call before the
 // LDS rows are used again.
+// tid / wave: the thread's and its wave's number inside the TEAM of four waves that runs the ray (a 256-thread workgroup is one
+// team; step_front_kernel's 1024-thread workgroups are four, each with its own ImpLds).  The three barriers are the WORKGROUP's:
+// every team executes them, also one without a ray in this trip (active = false, uniform over the team; `ray` must still be a
+// valid index), which does nothing else.
 struct ImpLds {
     float* wlds;     // [DEC_LDS] the SDF decoder only
     float* zu;       // jittered uniform samples
@@ -306,13 +311,13 @@ __device__ __forceinline__ void importance_row(const PlaneSet& planes, const esl
                                                const int ray, const int n_strat, const int n_imp,
                                                const float* __restrict__ t_free, const float* __restrict__ t_rand_uni,
                                                const float* __restrict__ u_rand, float* __restrict__ z_vals, const Rng& rng,
-                                               const ImpLds& L) {
+                                               const ImpLds& L, const int tid, const int wave, const bool active) {
     float* const wlds = L.wlds;
     float* const zu = L.zu;
     float* const wt = L.wt;
     float* const zn = L.zn;
     float* const al = L.al;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = tid & 63;
     const int r = lane & 15, q = lane >> 4;                                  // MFMA role (eslam_decode_tile.h)
     const int gp = gather_point<CL>(lane), gq = gather_piece<CL>(lane);     // gather role
     const float beta = dec.beta[0];
@@ -322,12 +327,12 @@ __device__ __forceinline__ void importance_row(const PlaneSet& planes, const esl
     const float far = __fadd_rn(aabb_exit_dev(o, d, bnd), 0.01f);          // Renderer.py:114-117
 
     // Renderer.py:119: near*(1-t) + far*t with near = 0
-    for (int i = threadIdx.x; i < n_strat; i += 256) {
+    for (int i = tid; i < n_strat && active; i += 256) {
         const float t = t_free[i];
         wt[i] = __fadd_rn(__fmul_rn(0.0f, __fsub_rn(1.0f, t)), __fmul_rn(far, t));
     }
     __syncthreads();                                 // (also: the decoder weights are staged)
-    for (int i = threadIdx.x; i < n_strat; i += 256)
+    for (int i = tid; i < n_strat && active; i += 256)
         zu[i] = t_rand_uni ? jitter_one(wt, i, n_strat, t_rand_uni[(int64_t)ray * n_strat + i])
                            : (rng.on && rng.perturb) ? jitter_one(wt, i, n_strat, rng_uniform(rng, 1u, (rng.ray_offset + (uint32_t)ray) * (uint32_t)n_strat + (uint32_t)i)) : wt[i];
     __syncthreads();
@@ -335,7 +340,7 @@ __device__ __forceinline__ void importance_row(const PlaneSet& planes, const esl
     // SDF decode of the n_strat points (geometry planes only) -> alpha (Renderer.py:122-127); wave w takes blocks w, w+4, ...
     const int nblk = (n_strat + 15) >> 4;
 #pragma unroll 1
-    for (int b = wave; b < nblk; b += 4) {
+    for (int b = wave; b < nblk && active; b += 4) {
         const int oz0 = opaque_zero(b);
         const float z = zu[min(16 * b + gp, n_strat - 1)];
         // Renderer.py:122: o + d*z (mul then add, as torch does)
@@ -357,7 +362,7 @@ __device__ __forceinline__ void importance_row(const PlaneSet& planes, const esl
         }
     }
     __syncthreads();
-    if (wave != 0) return;
+    if (wave != 0 || !active) return;
 
     // transmittance and weights (Renderer.py:128-129), 64 samples at a time
     float trans_in = 1.0f;
@@ -480,7 +485,7 @@ __global__ __launch_bounds__(256, WITH_DEPTH ? 4 : 2) void importance_z_kernel(c
         const int ray = blockIdx.x;
         if (gt_depth[ray] > 0.0f) return;            // uniform over the workgroup
         stage_decoder_weights_one(wlds, dec, 0, threadIdx.x, blockDim.x);
-        importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, t_rand_uni, u_rand, z_vals, rng, L);
+        importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, t_rand_uni, u_rand, z_vals, rng, L, (int)threadIdx.x, (int)threadIdx.x >> 6, true);
         return;
     }
     const int less_wgs = (int)gridDim.x - row_wgs;
@@ -538,9 +543,116 @@ __global__ __launch_bounds__(256, WITH_DEPTH ? 4 : 2) void importance_z_kernel(c
         unsigned long long bits = less_bits[lo];
         for (int skip = idx - (int)less_before[lo]; skip > 0; --skip) bits &= bits - 1ull;       // < 64 trips
         const int ray = seg_base + 64 * lo + (int)__builtin_ctzll(bits);
-        importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, t_rand_uni, u_rand, z_vals, rng, L);
+        importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, t_rand_uni, u_rand, z_vals, rng, L, (int)threadIdx.x, (int)threadIdx.x >> 6, true);
         __syncthreads();                             // the rows are free for the next ray
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The front of a training step as ONE launch on the step's own stream (eslam_step_front): what ray_order_kernel (ordering +
+// gradient clear) and importance_z_kernel<., true> (both sampler roles) do in two launches on two streams, as four roles of
+// 1024-thread workgroups chosen by the block number, the long ones in front:
+//   [0, n_order)    ordering: ray_order_block (eslam_ray_order_dev.h; contraction pinned ON there, OFF for this file's own code)
+//   + n_less        depth-less rays.  A workgroup is FOUR TEAMS of four waves, each with its own LDS rows and its own staged SDF
+//                   decoder; the teams of a segment's seg_blocks workgroups take the segment's depth-less rays round robin (team
+//                   4 k + t of the segment: rays number 4 k + t, + seg_teams, ...) and run importance_row in lock-step: the
+//                   barriers inside are the workgroup's, the trip count is that of the workgroup's team 0, and a team without a
+//                   ray in a trip only keeps the barriers.  The chip holds as many teams as it held importance_z workgroups.
+//   + n_clear       gradient clear: ray_clear_block.  In front of the rows, so that its 27 - 70 MB of writes drain while the
+//                   ordering workgroups are still busy.
+//   + the rest      rows: wave w of block b writes the depth-guided row of ray 16 b + w when that ray has depth.
+// Dynamic LDS: the largest of the roles' needs (histogram + sorted ids / four teams' rows / sixteen waves' scratch rows), aliased.
+// ---------------------------------------------------------------------------------------------------------
+#define FRONT_TEAMS 4
+#define FRONT_TEAM_FLOATS (DEC_LDS + 4 * ESLAM_MAX_SAMPLES)
+static_assert(FRONT_TEAM_FLOATS % 4 == 0, "a team's LDS starts 16-byte aligned");
+static_assert(IMP_SEG == 1024, "one ballot word of the segment per wave of a 1024-thread workgroup");
+template <bool CL>
+__global__ __launch_bounds__(1024) void step_front_kernel(const PlaneSet planes, const eslam_decoders_t dec, const Bound bnd,
+                                                          const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                          const float* __restrict__ gt_depth, const int R, const int n_strat,
+                                                          const int n_imp, const float* __restrict__ t_free,
+                                                          float* __restrict__ z_vals, const float c15, const float c3,
+                                                          const float* __restrict__ t_surf, const RngArg rng_arg,
+                                                          int* __restrict__ perm, const int key_bits, const int n_order,
+                                                          const int n_less, const int seg_blocks, const int n_clear,
+                                                          float* __restrict__ clear, const long long clear_words) {
+    extern __shared__ __attribute__((aligned(16))) float front_lds[];
+    int b = (int)blockIdx.x;
+    if (b < n_order) {
+        ray_order_block(rays_o, rays_d, R, perm, key_bits, b, (unsigned*)front_lds);
+        return;
+    }
+    b -= n_order;
+    // (the wave's number through readfirstlane: the compiler then keeps what depends on it - the team, its LDS rows, `active`, the
+    // row role's ray - in scalar registers; the 128 vector registers of a 1024-thread workgroup are all in use)
+    const int lane = threadIdx.x & 63, wave16 = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    if (b < n_less) {
+        constexpr int NW = IMP_SEG / 64;                 // 64-ray ballot words of a segment: one per wave
+        __shared__ unsigned long long less_bits[NW];     // bit i of word w: ray 64 w + i of the segment is depth-less
+        __shared__ unsigned less_before[NW + 1];         // depth-less rays in front of word w; [NW]: of the segment
+        const int seg = b / seg_blocks, kb = b - seg * seg_blocks;
+        const int seg_base = seg * IMP_SEG;
+        const int seg_n = min(IMP_SEG, R - seg_base);
+        const int seg_teams = FRONT_TEAMS * seg_blocks;
+        if (seg_n <= 0 || FRONT_TEAMS * kb >= seg_n) return;       // (uniform) at most one team per ray
+        {
+            const int i = 64 * wave16 + lane;
+            const float dv = i < seg_n ? gt_depth[seg_base + i] : 1.0f;
+            const unsigned long long bits = __ballot(!(dv > 0.0f));
+            if (lane == 0) less_bits[wave16] = bits;
+        }
+        __syncthreads();
+        if (wave16 == 0) {                               // one word per lane
+            const unsigned c = lane < NW ? (unsigned)__popcll(less_bits[lane]) : 0u;
+            const unsigned incl = wave_incl_sum_u(c);
+            if (lane < NW) less_before[lane] = incl - c;
+            if (lane == NW - 1) less_before[NW] = incl;
+        }
+        __syncthreads();
+        const int total = (int)less_before[NW];          // <= seg_n <= R
+        if (FRONT_TEAMS * kb >= total) return;           // (uniform) nothing for this workgroup's first team, so for none
+        const Rng rng = make_rng(rng_arg);
+        const int team = wave16 >> 2, tid = threadIdx.x & 255, wave = wave16 & 3;
+        float* const tl = front_lds + team * FRONT_TEAM_FLOATS;
+        const ImpLds L = {tl, tl + DEC_LDS, tl + DEC_LDS + ESLAM_MAX_SAMPLES, tl + DEC_LDS + 2 * ESLAM_MAX_SAMPLES,
+                          tl + DEC_LDS + 3 * ESLAM_MAX_SAMPLES};
+        stage_decoder_weights_one(L.wlds, dec, 0, tid, 256);
+#pragma unroll 1
+        for (int idx0 = FRONT_TEAMS * kb; idx0 < total; idx0 += seg_teams) {      // (uniform over the workgroup)
+            const int idx = idx0 + team;
+            const bool active = idx < total;
+            int ray = seg_base;                          // a team without a ray: any valid one, nothing is written
+            if (active) {
+                // the word that holds the idx-th depth-less ray: the last w with less_before[w] <= idx (bisection over the NW words)
+                int lo = 0, hi = NW - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if ((int)less_before[mid] <= idx) lo = mid; else hi = mid - 1;
+                }
+                unsigned long long bits = less_bits[lo];
+                for (int skip = idx - (int)less_before[lo]; skip > 0; --skip) bits &= bits - 1ull;       // < 64 trips
+                ray = seg_base + 64 * lo + (int)__builtin_ctzll(bits);
+            }
+            importance_row<CL>(planes, dec, bnd, rays_o, rays_d, ray, n_strat, n_imp, t_free, nullptr, nullptr, z_vals, rng, L, tid, wave,
+                               active);
+            __syncthreads();                             // the rows are free for the next ray
+        }
+        return;
+    }
+    b -= n_less;
+    if (b < n_clear) {
+        ray_clear_block(clear, clear_words, b, n_clear);
+        return;
+    }
+    b -= n_clear;
+    const int ray = 16 * b + wave16;
+    if (ray >= R) return;
+    const float d0 = gt_depth[ray];
+    if (!(d0 > 0.0f)) return;                            // the depth-less role's
+    const Rng rng = make_rng(rng_arg);
+    depth_guided_row(d0, ray, n_strat, n_imp, c15, c3, t_free, t_surf, nullptr, z_vals + (int64_t)ray * (n_strat + n_imp),
+                     front_lds + wave16 * ESLAM_MAX_SAMPLES, lane, rng);
 }
 
 
@@ -777,12 +889,10 @@ extern "C" int eslam_importance_z(const eslam_plane_t* planes, const eslam_decod
     return eslam_check_launch("importance_z_kernel");
 }
 
-static int sample_z_all_impl(const char* who, const eslam_plane_t* planes, const eslam_decoders_t* dec,
-                             const float* bound6_host, const float* rays_o, const float* rays_d, const float* gt_depth,
-                             int R, int n_strat, int n_imp, double truncation, const float* t_free, const float* t_surf,
-                             const float* t_rand, const float* t_rand_uni, const float* u, const RngArg rng,
-                             float* z_vals, eslam_stream_t stream) {
-    if (R <= 0) return 0;
+// the argument checks of the one-launch samplers (R > 0): 1 = refused, the message is set
+static int sample_z_all_check(const char* who, const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                              const float* rays_o, const float* rays_d, const float* gt_depth, int R, int n_strat, int n_imp,
+                              const float* t_free, const float* t_surf, const float* u, const RngArg& rng, const float* z_vals) {
     if (n_strat < 3 || n_imp < 0 || n_strat + n_imp > ESLAM_MAX_SAMPLES) {
         eslam_set_error("%s: n_strat=%d n_imp=%d unsupported", who, n_strat, n_imp);
         return 1;
@@ -797,6 +907,27 @@ static int sample_z_all_impl(const char* who, const eslam_plane_t* planes, const
         return 1;
     }
     if (eslam_validate_planes(planes, 0, 6)) return 1;
+    return 0;
+}
+
+// workgroups of the chip's depth-less role: four 4-wave teams per CU
+static int sampler_resident_teams() {
+    static const int resident = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return 4 * (cus > 0 ? cus : 256);
+    }();
+    return resident;
+}
+
+static int sample_z_all_impl(const char* who, const eslam_plane_t* planes, const eslam_decoders_t* dec,
+                             const float* bound6_host, const float* rays_o, const float* rays_d, const float* gt_depth,
+                             int R, int n_strat, int n_imp, double truncation, const float* t_free, const float* t_surf,
+                             const float* t_rand, const float* t_rand_uni, const float* u, const RngArg rng,
+                             float* z_vals, eslam_stream_t stream) {
+    if (R <= 0) return 0;
+    if (sample_z_all_check(who, planes, dec, bound6_host, rays_o, rays_d, gt_depth, R, n_strat, n_imp, t_free, t_surf, u, rng, z_vals))
+        return 1;
     PlaneSet ps;
     for (int i = 0; i < NPL; ++i) ps.p[i] = planes[i < 6 ? i : i - 6];
     const Bound bnd = make_bound(bound6_host);
@@ -805,11 +936,7 @@ static int sample_z_all_impl(const char* who, const eslam_plane_t* planes, const
     // row role: four rays with depth per workgroup; depth-less role: per segment of IMP_SEG rays, the workgroups the chip holds
     // at once (four per CU: the kernel is built for four waves per SIMD) shared among the segments, at most one per ray of a
     // (full) segment
-    static const int resident = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 4 * (cus > 0 ? cus : 256);
-    }();
+    const int resident = sampler_resident_teams();
     const int row_wgs = (R + 3) / 4;
     const int nseg = (R + IMP_SEG - 1) / IMP_SEG;
     int seg_wgs = resident / nseg;
@@ -857,6 +984,65 @@ extern "C" int eslam_sample_z_all_rng(const eslam_plane_t* planes, const eslam_d
     rng.ray_offset = (uint32_t)ray_offset;
     return sample_z_all_impl("eslam_sample_z_all_rng", planes, dec, bound6_host, rays_o, rays_d, gt_depth, R, n_strat, n_imp,
                              truncation, t_free, t_surf, nullptr, nullptr, nullptr, rng, z_vals, stream);
+}
+
+extern "C" int eslam_step_front(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                                const float* rays_o, const float* rays_d, const float* gt_depth, int R, int n_strat, int n_imp,
+                                double truncation, const float* t_free, const float* t_surf, int perturb, uint64_t seed,
+                                const uint32_t* rng_state, int64_t ray_offset, float* z_vals, int32_t* perm, void* clear_ptr,
+                                int64_t clear_bytes, eslam_stream_t stream) {
+    const char* who = "eslam_step_front";
+    if (!perm && clear_bytes == 0)                       // nothing to order into, nothing to clear: the sampler alone
+        return eslam_sample_z_all_rng(planes, dec, bound6_host, rays_o, rays_d, gt_depth, R, n_strat, n_imp, truncation, t_free, t_surf,
+                                      perturb, seed, rng_state, ray_offset, z_vals, stream);
+    // every check of the two launches this one replaces, before anything is launched
+    if (ray_order_check_args(who, rays_o, rays_d, R, perm, clear_ptr, clear_bytes)) return 1;
+    if (R <= 0)                                          // no rays: the clear alone (eslam_ray_order_clear does the same)
+        return eslam_ray_order_clear(rays_o, rays_d, R, perm, clear_ptr, clear_bytes, stream);
+    if (ray_offset < 0 || (ray_offset + (int64_t)R) * (n_strat + n_imp) >= ((int64_t)1 << 32)) {
+        eslam_set_error("%s: ray_offset %lld out of range", who, (long long)ray_offset);
+        return 1;
+    }
+    RngArg rng;
+    rng.seed_lo = (uint32_t)seed; rng.seed_hi = (uint32_t)(seed >> 32); rng.state = rng_state; rng.on = 1;
+    rng.perturb = perturb ? 1 : 0;
+    rng.ray_offset = (uint32_t)ray_offset;
+    if (sample_z_all_check(who, planes, dec, bound6_host, rays_o, rays_d, gt_depth, R, n_strat, n_imp, t_free, t_surf, nullptr, rng, z_vals))
+        return 1;
+    PlaneSet ps;
+    for (int i = 0; i < NPL; ++i) ps.p[i] = planes[i < 6 ? i : i - 6];
+    const Bound bnd = make_bound(bound6_host);
+    const float c15 = (float)(1.5 * truncation);       // as eslam_sample_z
+    const float c3 = (float)(3.0 * truncation);
+    // depth-less role: per segment of IMP_SEG rays the teams the chip holds at once, shared among the segments, at most one per
+    // ray of a (full) segment - importance_z_kernel's workgroups, four to a workgroup here
+    const int nseg = (R + IMP_SEG - 1) / IMP_SEG;
+    int seg_teams = sampler_resident_teams() / nseg;
+    if (seg_teams < 1) seg_teams = 1;
+    if (seg_teams > (R < IMP_SEG ? R : IMP_SEG)) seg_teams = R < IMP_SEG ? R : IMP_SEG;
+    const int seg_blocks = (seg_teams + FRONT_TEAMS - 1) / FRONT_TEAMS;
+    const int key_bits = ray_order_key_bits(R);
+    const int n_order = ray_order_blocks(R), n_clear = ray_clear_blocks(clear_bytes);
+    const int64_t n_less = (int64_t)nseg * seg_blocks, n_row = ((int64_t)R + 15) / 16;
+    if (n_order + n_less + n_clear + n_row > 0x7FFFFFFF) {
+        eslam_set_error("%s: batch too large", who);
+        return 1;
+    }
+    size_t lds = (size_t)FRONT_TEAMS * FRONT_TEAM_FLOATS * sizeof(float);      // four teams' rows, unless the ordering or the row role needs more
+    if (lds < ray_order_lds_bytes(key_bits)) lds = ray_order_lds_bytes(key_bits);
+    if (lds < (size_t)16 * ESLAM_MAX_SAMPLES * sizeof(float)) lds = (size_t)16 * ESLAM_MAX_SAMPLES * sizeof(float);
+    dim3 grid((unsigned)(n_order + n_less + n_clear + n_row)), block(1024);
+    eslam_prof_begin(PROF_SAMPLE_Z, (hipStream_t)stream);
+    if (eslam_planes_channels_last(planes, 0, 6))
+        hipLaunchKernelGGL((step_front_kernel<true>), grid, block, lds, (hipStream_t)stream, ps, *dec, bnd, rays_o, rays_d, gt_depth, R,
+                           n_strat, n_imp, t_free, z_vals, c15, c3, t_surf, rng, perm, key_bits, n_order, (int)n_less, seg_blocks, n_clear,
+                           (float*)clear_ptr, (long long)(clear_bytes >> 2));
+    else
+        hipLaunchKernelGGL((step_front_kernel<false>), grid, block, lds, (hipStream_t)stream, ps, *dec, bnd, rays_o, rays_d, gt_depth, R,
+                           n_strat, n_imp, t_free, z_vals, c15, c3, t_surf, rng, perm, key_bits, n_order, (int)n_less, seg_blocks, n_clear,
+                           (float*)clear_ptr, (long long)(clear_bytes >> 2));
+    eslam_prof_end(PROF_SAMPLE_Z, (hipStream_t)stream);
+    return eslam_check_launch("step_front_kernel");
 }
 
 static int fill_set_sizes_args(const char* who, const float* gt_depth, const uint8_t* ray_mask, int R, int n_strat, int n_imp,

@@ -2,7 +2,7 @@
 // general path).  What Mapper.py:334-350 pays per iteration when it calls the library unchanged - no hipGraph - is host time:
 // the Python layer spent ~0.5 ms per iteration (descriptor building, ~15 tensor constructions, 5 ctypes calls, 4 stream
 // fork/joins, autograd glue) for 0.28 ms of GPU work.  Here ONE call does what Renderer.render_batch_ray does on its common
-// path - ray order + gradient clear on a side stream, sampler, forward (with the loss's sums when asked), join - and the autograd
+// path - the step's front (ray order, gradient clear and sampler: one launch), forward (with the loss's sums when asked) - and the autograd
 // node's backward is ONE call into eslam_render_bwd(_loss).  Everything goes through the C ABI of include/eslam_hip.h; PyTorch
 // is plumbing (tensors, the caller's stream, the autograd graph the reference's loops call .backward() on).
 //
@@ -16,6 +16,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -77,14 +78,19 @@ void fill_decoders(const std::vector<Tensor>& params, const Tensor& beta, eslam_
     d->beta = beta.data_ptr<float>();
 }
 
-// one side stream per device, owned by this module: the ray ordering and the gradient clear run there beside the sampler and
-// the forward kernel, forked and joined with events (valid inside a stream capture: they become graph edges)
+// one side stream per device, owned by this module, for the FORKED front only (render(..., forked_front=True): the ray ordering
+// and the gradient clear run there beside the sampler and the forward kernel, forked and joined with events - valid inside a
+// stream capture: they become graph edges).  The default front is one launch on the caller's stream and never creates it.
+std::atomic<int> side_streams_made{0};
 hipStream_t side_stream(int dev) {
     static std::mutex mu;
     static hipStream_t streams[64];
     TORCH_CHECK(dev >= 0 && dev < 64, "device index out of range");
     std::lock_guard<std::mutex> lk(mu);
-    if (!streams[dev]) TORCH_CHECK(hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking) == hipSuccess, "hipStreamCreate failed");
+    if (!streams[dev]) {
+        TORCH_CHECK(hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking) == hipSuccess, "hipStreamCreate failed");
+        ++side_streams_made;
+    }
     return streams[dev];
 }
 
@@ -146,6 +152,10 @@ public:
         bool relayout = false;
         // save the decoders' first hidden layer for the backward (ops.saved_hidden_on()); off: the backward recomputes it
         bool saved_hidden = true;
+        // the front of a call whose planes take a gradient: false = ONE launch on the caller's stream (eslam_step_front: ordering,
+        // clear and sampler); true = the earlier one, ordering + clear forked to the side stream and joined behind the forward
+        // kernel (tests and A/B measurements)
+        bool forked_front = false;
     };
 
     static variable_list forward(AutogradContext* ctx, at::TensorList in, const IO& io) {
@@ -186,20 +196,30 @@ public:
         eslam_decoders_t dd;
         fill_decoders(params, beta, &dd);
 
-        // side stream: gradient clear (27-70 MB) + ray order, beside the sampler and the forward kernel
+        // the front: gradient clear (27-70 MB), ray order and sampler as one launch on this stream (tracking - planes without a
+        // gradient - has only the sampler); forked_front: clear + order on the side stream, beside the sampler and the forward kernel
         std::vector<Tensor> grad_views;
         Tensor grad_flat;
         hipStream_t side = nullptr;
-        if (planes_grad && R > 0) {       // (tracking - planes without a gradient - has nothing for the side stream to do)
-            side = side_stream(dev);
+        if (planes_grad && R > 0) {
             auto gv = alloc_plane_grads(planes);
             grad_flat = gv.first;
             grad_views = std::move(gv.second);
-            check(eslam_stream_wait(side, st), "eslam_stream_wait");
-            check(eslam_ray_order_clear(rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), (int)R, perm.data_ptr<int32_t>(),
-                                        grad_flat.data_ptr<float>(), grad_flat.numel() * 4, side), "eslam_ray_order_clear");
+            if (io.forked_front) {
+                side = side_stream(dev);
+                check(eslam_stream_wait(side, st), "eslam_stream_wait");
+                check(eslam_ray_order_clear(rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), (int)R, perm.data_ptr<int32_t>(),
+                                            grad_flat.data_ptr<float>(), grad_flat.numel() * 4, side), "eslam_ray_order_clear");
+            }
         }
-        if (R > 0) {
+        if (planes_grad && R > 0 && !io.forked_front) {
+            check(eslam_step_front(pd, &dd, io.cfg.bound_sample.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),
+                                   gd.data_ptr<float>(), (int)R, (int)io.cfg.n_strat, (int)io.cfg.n_imp, io.cfg.truncation,
+                                   io.t_free.data_ptr<float>(), io.t_surf.data_ptr<float>(), io.cfg.perturb ? 1 : 0, io.seed,
+                                   (const uint32_t*)io.rng_state.data_ptr<int32_t>(), io.ray_offset, z.data_ptr<float>(),
+                                   perm.data_ptr<int32_t>(), grad_flat.data_ptr<float>(), grad_flat.numel() * 4, st),
+                  "eslam_step_front");
+        } else if (R > 0) {
             check(eslam_sample_z_all_rng(pd, &dd, io.cfg.bound_sample.data(), rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),
                                          gd.data_ptr<float>(), (int)R, (int)io.cfg.n_strat, (int)io.cfg.n_imp, io.cfg.truncation,
                                          io.t_free.data_ptr<float>(), io.t_surf.data_ptr<float>(), io.cfg.perturb ? 1 : 0, io.seed,
@@ -421,13 +441,13 @@ std::vector<Tensor> render(const Config& cfg, const Tensor& rays_o, const Tensor
                            const std::vector<Tensor>& planes, const std::vector<Tensor>& params, const Tensor& t_free, const Tensor& t_surf,
                            const Tensor& rng_state, uint64_t seed, int64_t ray_offset, const c10::optional<Tensor>& gt_color,
                            const c10::optional<Tensor>& ray_mask, const c10::optional<Tensor>& scratch, const c10::optional<Tensor>& acc_out,
-                           const std::vector<double>& weights5, bool relayout, bool saved_hidden) {
+                           const std::vector<double>& weights5, bool relayout, bool saved_hidden, bool forked_front) {
     TORCH_CHECK(cfg.n_strat >= 3 && cfg.bound_sample.size() == 6 && cfg.bound_decode.size() == 6, "Config not initialised");
     TORCH_CHECK(planes.size() == 12 && params.size() == 12, "expected 12 planes and 12 decoder tensors");
     RenderNode::IO io;
     io.cfg = cfg;
     io.gt_depth = gt_depth; io.t_free = t_free; io.t_surf = t_surf; io.rng_state = rng_state;
-    io.seed = seed; io.ray_offset = ray_offset; io.relayout = relayout; io.saved_hidden = saved_hidden;
+    io.seed = seed; io.ray_offset = ray_offset; io.relayout = relayout; io.saved_hidden = saved_hidden; io.forked_front = forked_front;
     TORCH_CHECK(t_free.numel() == cfg.n_strat && t_surf.numel() == cfg.n_imp && rng_state.scalar_type() == at::kInt, "bad sampler tensors");
     if (gt_color.has_value()) {
         TORCH_CHECK(scratch.has_value() && weights5.size() == 5, "the fused loss needs its scratch and 5 weights");
@@ -466,7 +486,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("render", &render, py::arg("cfg"), py::arg("rays_o"), py::arg("rays_d"), py::arg("gt_depth"), py::arg("beta"), py::arg("planes"),
           py::arg("params"), py::arg("t_free"), py::arg("t_surf"), py::arg("rng_state"), py::arg("seed"), py::arg("ray_offset"),
           py::arg("gt_color") = py::none(), py::arg("ray_mask") = py::none(), py::arg("scratch") = py::none(), py::arg("acc_out") = py::none(),
-          py::arg("weights5") = std::vector<double>(), py::arg("relayout") = false, py::arg("saved_hidden") = true);
+          py::arg("weights5") = std::vector<double>(), py::arg("relayout") = false, py::arg("saved_hidden") = true, py::arg("forked_front") = false);
+    m.def("side_streams_created", []() { return side_streams_made.load(); },
+          "side streams this module has created: 0 in a process that only ran the one-launch front");
     m.def("mapping_loss", &mapping_loss, py::arg("depth"), py::arg("rgb"), py::arg("sdf"), py::arg("z_vals"), py::arg("gt_depth"),
           py::arg("gt_color"), py::arg("truncation"), py::arg("weights5"), py::arg("ray_mask"), py::arg("scratch"));
     m.def("abi_version", []() { return eslam_abi_version(); });

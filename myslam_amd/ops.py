@@ -288,6 +288,47 @@ def ray_order_async(rays_o, rays_d, grad_planes=None):
     return (perm, side) if pre is None else (perm, side, pre[1])
 
 
+def step_front_ok(n_strat, rand):
+    """Whether a training call may take the one-launch front: the sampler draws its own random numbers (as ext_render_ok asks),
+    and nobody else owns the gradient buffer or the random-number step (the ray-sharded mapper keeps its own prologue)."""
+    return (rand is None and _USE_KERNEL_RNG and n_strat >= 3 and _grad_sink is None and not _keep_layout and
+            _rng_override is None)
+
+
+def step_front(rays_o, rays_d, gt_depth, flat_planes, decoders, bound6, truncation, n_strat, n_imp, perturb):
+    """The front of a training step as ONE launch on the current stream (eslam_step_front): the three ray orders, the clear of
+    the plane-gradient buffer (allocated here) and the samplers' z_vals - what ray_order_async + sample_z do in two launches
+    on two streams.  Nothing is forked, so nothing has to be joined.
+    Returns (z_vals [R, S], perm int32 [3 R + 4], the 12 pre-cleared gradient views)."""
+    _hip.require_gpu_f32("rays_o", rays_o)
+    _hip.require_gpu_f32("rays_d", rays_d)
+    _hip.require_gpu_f32("gt_depth", gt_depth)
+    if not step_front_ok(n_strat, None):
+        raise RuntimeError("ops.step_front: needs the in-kernel random numbers, n_stratified >= 3 and no gradient sink; use "
+                           "ray_order_async + sample_z")
+    dev = rays_o.device
+    ro, rd, gd = _c(rays_o.detach()), _c(rays_d.detach()), _c(gt_depth.detach().reshape(-1))
+    R = gd.shape[0]
+    z = torch.empty(R, n_strat + n_imp, device=dev)
+    perm = torch.empty(_hip.ray_order_words(R), dtype=torch.int32, device=dev)
+    pre = _alloc_plane_grads(flat_planes, zero=False)
+    t_free, t_surf = linspace01(n_strat, dev), linspace01(n_imp, dev)
+    seed_v = _rng_seed(dev)
+    state = _rng_state(dev)
+    if _rng_pending.get(dev.index, False):
+        state[0] += 1                  # the previous samples were never rendered: advance the step here
+    arr, _ = _hip.make_planes(flat_planes)
+    dec, keep = _hip.make_decoders(decoder_params(decoders), beta_tensor(decoders.beta, dev))
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_step_front(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(ro), _hip.ptr(rd),
+                                               _hip.ptr(gd), R, n_strat, n_imp, float(truncation), _hip.ptr(t_free),
+                                               _hip.ptr(t_surf), 1 if perturb else 0, seed_v, _hip.ptr(state), _ray_offset,
+                                               _hip.ptr(z), _hip.ptr(perm), _hip.ptr(pre[0]), pre[0].numel() * 4,
+                                               _hip.stream_handle(dev)), "eslam_step_front")
+    _rng_pending[dev.index] = True
+    return z, perm, pre[1]
+
+
 _fused_loss = None
 
 # A float32 render call that will be back-propagated also saves the decoders' first hidden layer (128 bytes per sample beside
@@ -368,9 +409,10 @@ def ext_render_ok(rays_o, n_strat, rand):
             _rng_override is None and rays_o.is_cuda and torch_ext() is not None)
 
 
-def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_strat, n_imp, fl, relayout=False, saved_hidden=None):
-    """One compiled call: [planes -> channels-last scratch when `relayout`,] ray order + gradient clear (side stream), sampler,
-    forward (+ the loss's sums), join.  fl: the active ops.fused_loss context or None.  Returns depth, rgb, sdf, z_vals."""
+def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_strat, n_imp, fl, relayout=False, saved_hidden=None,
+               forked_front=False):
+    """One compiled call: [planes -> channels-last scratch when `relayout`,] the front (ray order, gradient clear and sampler as
+    one launch; forked_front: order + clear on a side stream, joined behind the forward), forward (+ the loss's sums).  fl: the active ops.fused_loss context or None.  Returns depth, rgb, sdf, z_vals."""
     dev = rays_o.device
     seed_v = _rng_seed(dev)
     state = _rng_state(dev)
@@ -382,14 +424,14 @@ def ext_render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, n_s
     with _hip.on_device(dev):
         if fl is None:
             outs = ext.render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, linspace01(n_strat, dev), linspace01(n_imp, dev),
-                              state, seed_v, _ray_offset, relayout=relayout, saved_hidden=keep_h)
+                              state, seed_v, _ray_offset, relayout=relayout, saved_hidden=keep_h, forked_front=bool(forked_front))
         else:
             mask = fl.ray_mask
             if mask is not None:
                 mask = _c(mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8))
             outs = ext.render(cfg, rays_o, rays_d, gt_depth, beta, flat_planes, dec_params, linspace01(n_strat, dev), linspace01(n_imp, dev),
                               state, seed_v, _ray_offset, fl.gt_color, mask, _loss_scratch(dev, rays_o.shape[0]), fl.acc_out,
-                              list(fl.state.weights5), relayout, keep_h)
+                              list(fl.state.weights5), relayout, keep_h, bool(forked_front))
             fl.loss, fl.acc = outs[4], outs[5]
             fl.value = outs[4].detach()
     return outs[0], outs[1], outs[2], outs[3]
@@ -632,7 +674,8 @@ class RenderFn(torch.autograd.Function):
     decoders' first hidden layer for its backward; not given = ops.saved_hidden_on().
 
     Forward = eslam_render_fwd, backward = eslam_render_bwd (reference: Renderer.py:136-147 and its autograd).
-    order = (perm, stream) from ray_order_async, or None.
+    order = (perm, stream[, pre-cleared gradient views]) from ray_order_async, (perm, None, views) from step_front - made on
+    this stream, nothing to join - or None.
     lossctx = an ops.fused_loss context or None.  With it the forward is eslam_render_fwd_loss, a fourth output `loss`
     (0-d) is returned, and the gradient arriving on it is turned into the rendered outputs' gradients inside the backward
     kernel (eslam_render_bwd_loss); gradients arriving on depth / rgb / sdf themselves are added as usual."""

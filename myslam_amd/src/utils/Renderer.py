@@ -21,11 +21,14 @@ class Renderer(object):
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = eslam.H, eslam.W, eslam.fx, eslam.fy, eslam.cx, eslam.cy
 
     def render_batch_ray(self, all_planes, decoders, rays_d, rays_o, device, truncation, gt_depth=None, _rand=None,
-                         saved_hidden=None):
+                         saved_hidden=None, forked_front=False):
         """Renderer.py:63-147.  NB argument order (rays_d, rays_o).  Returns depth [R], rgb [R,3], sdf [R,S],
         z_vals [R,S].  `_rand` (tests only) injects the three uniform tensors instead of drawing them.
         saved_hidden: True / False = the backward of this call reads the first hidden layer the forward saved / recomputes it
-        (same bits either way); None = ops.saved_hidden_on().  Handed down as a plain argument."""
+        (same bits either way); None = ops.saved_hidden_on().  Handed down as a plain argument.
+        forked_front (tests and A/B measurements): True = a training call orders its rays and clears its gradient buffer on a
+        side stream, beside the sampler, and joins behind the forward kernel - the front before ops.step_front, which does
+        all three in one launch on the call's own stream.  A plain argument as well."""
         keep_h = ops.saved_hidden_on() if saved_hidden is None else bool(saved_hidden)
         n_rays = rays_o.shape[0]
         S = self.n_stratified + self.n_importance
@@ -40,21 +43,28 @@ class Renderer(object):
             # the common case as ONE compiled call (eslam_torch_ext.cpp); everything below is the same sequence through ctypes
             return ops.ext_render(self._ext_cfg(truncation, decoders), rays_o, rays_d, gt_depth, beta,
                                   [p for grp in all_planes for p in grp], ops.decoder_params(decoders), self.n_stratified,
-                                  self.n_importance, ops.current_fused_loss(), ops.wants_relayout(all_planes, n_rays * S), keep_h)
+                                  self.n_importance, ops.current_fused_loss(), ops.wants_relayout(all_planes, n_rays * S), keep_h,
+                                  forked_front)
         # planes in the reference's NCHW layout: per-call channels-last scratch copies (gradients flow back through them)
         all_planes = ops.planes_for_kernels(all_planes, n_rays * S)
         flat_planes = [p for grp in all_planes for p in grp]
-        # training calls get a direction-sorted ray order (better L2 locality forward, bundling for the scatter); it only
-        # depends on the rays, so it runs on a side stream next to the samplers
+        # training calls get a direction-sorted ray order (bundling for the scatter) and a cleared gradient buffer: roles of the
+        # sampler's own launch (ops.step_front), or - forked_front, injected random numbers, a gradient sink - a launch on a side
+        # stream next to the samplers
         grad_on = torch.is_grad_enabled()
         planes_grad = grad_on and any(p.requires_grad for p in flat_planes)
         wants_grad = planes_grad or (grad_on and (rays_o.requires_grad or rays_d.requires_grad or
                                                   any(p.requires_grad for p in ops.decoder_params(decoders)) or
                                                   (torch.is_tensor(decoders.beta) and decoders.beta.requires_grad)))
         # (the order bundles rays for the plane-gradient scatter; a call whose planes take no gradient - tracking - has no use for it)
-        order = ops.ray_order_async(rays_o, rays_d, flat_planes) if planes_grad else None
-        z_vals = ops.sample_z(rays_o, rays_d, gt_depth, all_planes, decoders, self._bound6, truncation,
-                              self.n_stratified, self.n_importance, self.perturb, _rand)
+        if planes_grad and not forked_front and ops.step_front_ok(self.n_stratified, _rand):
+            z_vals, perm, pre = ops.step_front(rays_o, rays_d, gt_depth, flat_planes, decoders, self._bound6, truncation,
+                                               self.n_stratified, self.n_importance, self.perturb)
+            order = (perm, None, pre)           # no stream: RenderFn joins nothing
+        else:
+            order = ops.ray_order_async(rays_o, rays_d, flat_planes) if planes_grad else None
+            z_vals = ops.sample_z(rays_o, rays_d, gt_depth, all_planes, decoders, self._bound6, truncation,
+                                  self.n_stratified, self.n_importance, self.perturb, _rand)
         # pts are normalised with decoders.bound (decoders.py:138), the importance sampler uses renderer.bound
         bound6 = ops.bound_to_host(decoders.bound)
         fl = ops.current_fused_loss()          # set by render_batch_ray_with_loss
@@ -83,13 +93,14 @@ class Renderer(object):
         return d
 
     def render_batch_ray_with_loss(self, all_planes, decoders, rays_d, rays_o, device, truncation, gt_depth, gt_color,
-                                   weights, ray_mask=None, _rand=None, acc_out=None, saved_hidden=None):
+                                   weights, ray_mask=None, _rand=None, acc_out=None, saved_hidden=None, forked_front=False):
         """render_batch_ray + the mapping loss (src/Mapper.py:337-346): its sums are formed in the forward kernel's
         epilogue and its gradients inside the backward kernel.  Returns (depth, rgb, sdf, z_vals, pre); pre.loss is the
         loss (losses.mapping_loss(..., precomputed=pre) returns it): call .backward() on it."""
         with ops.fused_loss(gt_depth, gt_color, truncation, weights, ray_mask, acc_out=acc_out) as pre:
             depth, rgb, sdf, z_vals = self.render_batch_ray(all_planes, decoders, rays_d, rays_o, device, truncation,
-                                                            gt_depth=gt_depth, _rand=_rand, saved_hidden=saved_hidden)
+                                                            gt_depth=gt_depth, _rand=_rand, saved_hidden=saved_hidden,
+                                                            forked_front=forked_front)
         return depth, rgb, sdf, z_vals, pre
 
     def sdf2alpha(self, sdf, beta=10):

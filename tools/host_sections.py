@@ -9,12 +9,12 @@ def wrap(obj, name, label=None):
     def g(*a, **k):
         t = time.perf_counter(); r = f(*a, **k); acc[label] += time.perf_counter() - t; return r
     setattr(obj, name, staticmethod(g) if isinstance(obj, type) and name in ('forward', 'backward') else g)
-wrap(ops, 'sample_z'); wrap(ops, 'ray_order_async')
+wrap(ops, 'step_front'); wrap(ops, 'sample_z'); wrap(ops, 'ray_order_async')      # (the last two: tracking and the forked front)
 wrap(ops.RenderFn, 'forward', 'RenderFn.forward'); wrap(ops.RenderFn, 'backward', 'RenderFn.backward')
 wrap(ops.MappingLossFn, 'forward', 'Loss.forward'); wrap(ops.MappingLossFn, 'backward', 'Loss.backward')
 wrap(_hip, 'make_planes'); wrap(_hip, 'make_decoders'); wrap(ops, 'decoder_params'); wrap(_hip, 'stream_handle')
 lib = _hip.lib()
-for fn in ('eslam_render_fwd', 'eslam_render_bwd', 'eslam_sample_z_all', 'eslam_loss_value', 'eslam_loss_grad', 'eslam_ray_order'):
+for fn in ('eslam_render_fwd', 'eslam_render_bwd', 'eslam_step_front', 'eslam_sample_z_all', 'eslam_loss_value', 'eslam_loss_grad', 'eslam_ray_order'):
     f = getattr(lib, fn)
     def mk(f, fn):
         def g(*a):
