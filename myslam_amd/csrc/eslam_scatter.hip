@@ -66,10 +66,11 @@ __global__ __launch_bounds__(1024) void ray_order_kernel(const float* __restrict
 // contribution did not touch).  A texel's SUM that leaves +-5.2e5 while every contribution is in range wraps undetected.
 struct ShadowOff { int64_t o[NPL]; };
 // GZ (the rank-16 path, see mlp_bwd_kernel): g_feat holds gz[2][N][16], the gradient at the decoders' first hidden layer, and
-//   the features' gradient W1^T . g_z1 is never formed per sample.  The walk sums w * g_z1 per cell in the 16-wide space - lane
-//   (hx = lane >> 5, row = (lane >> 4) & 1, j = lane & 15), ONE accumulator, one 64-byte row per entry shared by the six planes of
-//   a decoder - and the flush multiplies the cell's 2 x 2 x 16 sums by the plane's [16, 32] slice of W1 (LDS, staged once per
-//   workgroup) before the same two atomics per lane (hx, c).  tests/rank16_ref.py restates the bookkeeping in numpy.
+//   the features' gradient W1^T . g_z1 is never formed per sample.  The walk sums w * g_z1 per cell in the 16-wide space - four
+//   sorted entries per step, lane (slot = lane >> 4, j = lane & 15) with the entry's four corner sums, one 64-byte row per entry
+//   shared by the six planes of a decoder - and the flush adds the slots and multiplies the cell's 2 x 2 x 16 sums by the plane's
+//   [16, 32] slice of W1 (LDS, staged once per workgroup) before the same two atomics per lane (hx, c).  tests/rank16_ref.py
+//   states what is computed, tests/quad_walk_ref.py restates the walk's bookkeeping in numpy.
 constexpr int SC_NT = 512;
 constexpr int GZ_WP = 20;                           // pitch (floats) of the W1 slice's rows [c][j]: 16-byte aligned, conflict-free
 template <bool RENDER, bool DET, int SPT = 4, bool GZ = false>
@@ -394,34 +395,155 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     const unsigned dm_bytes = (unsigned)(swap ? psy : psx) << 2, dM_bytes = (unsigned)(swap ? psx : psy) << 2;
     char* __restrict__ gbytes = DET ? (char*)(shadow + shoff.o[pi]) : (char*)grad;
     float* const gz_as = gz_a + (GZ ? wave * WAVE : 0);
+    if constexpr (GZ) {
+        // The rank-16 walk: four consecutive sorted entries per step.  Lane (slot s = lane >> 4, j = lane & 15) takes entry
+        // 4 t + s of step t: ONE 16-byte LDS read of the entry's four weights, ONE row load (the four slots fetch four 64-byte
+        // rows with one instruction, the row number comes from LDS: no v_readlane), two packed FMAs into the four sums
+        // k = 2 hx + row - and one scalar test of the step's four `fresh` bits.  A cell's sums are thus held as four partial
+        // sums per (k, j), one per slot; the flush adds them.  tests/quad_walk_ref.py restates the bookkeeping in numpy.
+        //   (One entry per step - 64 lanes (hx, row, j), every row load fetching 16 distinct floats into 64 lanes, v_readlane +
+        //   load + LDS read + bit test + wait + FMA + branch per entry - was 4-5 us slower in the walk and, with its flush's two
+        //   more LDS round trips, 12-13 us in all: DESIGN.md section 5 "Four entries per step".)
+        // (the lane-derived addresses of the walk are formed HERE: derived from `lane` itself the compiler forms them at the kernel's
+        // start and keeps them through the cell and sort phases, whose registers are the kernel's peak)
+        int wl = lane;
+        asm volatile("" : "+v"(wl));
+        const int s = wl >> 4, whx = wl >> 5, wc = wl & 31;    // accumulating role (s, j); flushing role (hx, c)
+        const unsigned wlane_off = (unsigned)(wc * psc) << 2;
+        const int up1 = ((wl + WAVE - 1) & (WAVE - 1)) << 2;         // ds_bpermute address of the lane below
+        float2_t alo = {0.f, 0.f}, ahi = {0.f, 0.f};             // k = 0, 1 (hx = 0: rows 0, 1) and k = 2, 3 (hx = 1)
+        // Flush of a finished cell.  The slots' partial sums are added by a transposing exchange - lane bit 4, then lane bit 5 -
+        // after which lane (s, j) holds the cell's sum for k = s: the layout gz_as[k * 16 + j] the expansion reads.  Then lane
+        // (hx, c) forms sum_j W1[j][c] A[hx][row][j] for rows 0 and 1 - the cell's 64 sums through the wave's 256 bytes of LDS (a
+        // half-wave reads ONE address: broadcast), the slice's row c from gz_w - and adds them with two atomics as the walk below.
+        // The flush is what a wave WAITS for (every LDS round trip in it showed in the kernel's time), so it has as few as the
+        // registers allow.
+        auto flush4 = [&](const bool lower_half_only) {
+            if (cur_xy == PAD_XY) return;
+            // v_permlane16_swap: rows 1 and 3 (16 lanes each) of the first operand <-> rows 0 and 2 of the second; the sum of the
+            // two results is k = (s & 1) over slots s and s ^ 1 (alo) and k = 2 + (s & 1) (ahi).  v_permlane32_swap: lanes 32-63 of
+            // the first <-> lanes 0-31 of the second; the sum is k = s over all four slots.
+            // (inline assembly with the two wait states a VALU-written operand needs inside the string: hipcc 7.x folds the sum
+            // of the builtin's two results into twice the first one)
+            float x0 = alo[0], y0 = alo[1], x1 = ahi[0], y1 = ahi[1];
+            asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x0), "+v"(y0));
+            asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x1), "+v"(y1));
+            float r0 = x0 + y0, r1 = x1 + y1;
+            asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(r0), "+v"(r1));
+            gz_as[wl] = r0 + r1;
+            WAVE_SYNC();
+            const float4_t* const A = (const float4_t*)(gz_as + whx * 32);
+            // (the slice's row is read anew in every flush: as a loop invariant the compiler keeps its 16 values in registers, so
+            // the row's offset is made opaque to it)
+            unsigned wrow = (unsigned)(wc * GZ_WP);
+            asm volatile("" : "+v"(wrow));
+            const float4_t* const Wc = (const float4_t*)(gz_w + wrow);
+            float f0 = 0.0f, f1 = 0.0f;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const float4_t v0 = A[jj], v1 = A[4 + jj], wv = Wc[jj];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { f0 += wv[i] * v0[i]; f1 += wv[i] * v1[i]; }
+                // summed where they stand: six reads at a time (24 registers; all twelve in flight would take 48; three at a
+                // time were 3 us slower), three at a time in the 1024-sample kernel, whose eight waves per SIMD leave 64 registers
+                if ((jj & 1) || SPT == 2) asm volatile("" : "+v"(f0), "+v"(f1));
+            }
+            WAVE_SYNC();                                  // (the next flush's write stays behind these reads)
+            const unsigned o0 = (cur_xy & ~3u) + wlane_off + ((cur_xy & 1u) & (unsigned)whx) * dm_bytes;
+            const unsigned o1 = o0 + ((cur_xy >> 1) & 1u) * dM_bytes;
+            if (!lower_half_only || whx == 0) {
+                atomicAdd((float*)(gbytes + o0), f0);
+                atomicAdd((float*)(gbytes + o1), f1);
+            }
+        };
+        struct Rec4 { unsigned xy; unsigned long long fresh, adjacent; };
+        auto fetch4 = [&](int blk, unsigned prev_last) {
+            Rec4 r;
+            r.xy = sxy[e0 + blk * WAVE + wl];
+            unsigned prev = (unsigned)__builtin_amdgcn_ds_bpermute(up1, (int)r.xy);
+            if (wl == 0) prev = prev_last;
+            const bool fresh = r.xy != prev;
+            const bool adj = fresh && r.xy != PAD_XY && prev != PAD_XY && (prev & 1u) && (r.xy & ~3u) == (prev & ~3u) + dm_bytes;
+            r.fresh = __ballot(fresh);
+            r.adjacent = __ballot(adj);
+            return r;
+        };
+        // A step with a `fresh` bit.  For every fresh entry kk, in order: the step's entries in front of it that are not yet
+        // summed (slots < kk) still belong to the cell it closes; then the flush; then - next cell along the minor axis: its first
+        // texel column is our second one - every lane keeps ITS OWN partial sums of that column (ahi -> alo: the slots are added
+        // at the next flush anyway).  What is left in g - the slots from the last fresh entry on - is added by the step itself.
+        auto close_cell = [&](const Rec4& rec, const int e, const int kk, const bool carry, const float4_t w4, float& g) {
+            const float gk = (s < kk) ? g : 0.f;                // (selected, not multiplied: a padding entry's row is row 0)
+            g = (s < kk) ? 0.f : g;
+            alo += gk * w4.xy;
+            ahi += gk * w4.zw;
+            flush4(carry);
+            alo = carry ? ahi : (float2_t){0.f, 0.f};
+            ahi = (float2_t){0.f, 0.f};
+            cur_xy = (unsigned)__builtin_amdgcn_readlane((int)rec.xy, e + kk);
+        };
+        // rows are requested WALK_Q steps (16 entries) ahead, two groups in flight: loads issued behind an atomic wait for it
+        constexpr int WALK_Q = 4;
+        const __amdgpu_buffer_rsrc_t grsrc4 = __builtin_amdgcn_make_buffer_rsrc((void*)gcol, 0, (int)((unsigned)npts * 64u), 0x00020000);
+        const int j4 = (wl & 15) * 4;
+        const int* const rlane = sgrow + s;                    // + the step's first entry
+        const float4_t* const wlane4 = sw + s;
+#define LOAD_Q(buf, eb, grp)                                                                  \
+    _Pragma("unroll") for (int t = 0; t < WALK_Q; ++t) {                                      \
+        const int row = rlane[(eb) + 4 * ((grp) * WALK_Q + t)];                               \
+        buf[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grsrc4, (row << 6) + j4, 0, 0)); \
+    }
+#define WALK_Q4(buf, rec, grp, eb)                                                            \
+    _Pragma("unroll") for (int t = 0; t < WALK_Q; ++t) {                                      \
+        const int st = (grp) * WALK_Q + t;                                                    \
+        const float4_t w4 = wlane4[(eb) + 4 * st];                                            \
+        const unsigned nib = ((st < 8 ? fresh_lo : fresh_hi) >> (4 * (st & 7))) & 15u;        \
+        float g = buf[t];                                                                     \
+        for (unsigned m = nib; __builtin_expect(m != 0u, 0); m &= m - 1u) {                   \
+            const int kk = __builtin_ctz(m);                                                  \
+            close_cell(rec, 4 * st, kk, ((st < 8 ? adj_lo : adj_hi) >> (4 * (st & 7) + kk)) & 1u, w4, g); \
+        }                                                                                     \
+        alo += g * w4.xy;           /* padding entries have zero weights and belong to no cell */ \
+        ahi += g * w4.zw;                                                                     \
+    }
+        constexpr int nblk = CH / WAVE;
+        constexpr int ngrp = WAVE / (4 * WALK_Q);              // groups per 64-entry record block (even)
+        float ga[WALK_Q], gb[WALK_Q];
+        Rec4 rec = fetch4(0, PAD_XY);
+        LOAD_Q(ga, e0, 0)
+#pragma unroll 1
+        for (int blk = 0; blk < nblk; ++blk) {
+            if ((unsigned)__builtin_amdgcn_readfirstlane((int)rec.xy) == PAD_XY) break;   // sorted: everything from here is padding
+            last_xy = (unsigned)__builtin_amdgcn_readlane((int)rec.xy, WAVE - 1);
+            Rec4 nxt = rec;
+            if (blk + 1 < nblk) nxt = fetch4(blk + 1, last_xy);
+            const int ebase = e0 + blk * WAVE;
+            const unsigned fresh_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)rec.fresh);
+            const unsigned fresh_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rec.fresh >> 32));
+            const unsigned adj_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)rec.adjacent);
+            const unsigned adj_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rec.adjacent >> 32));
+#pragma unroll
+            for (int g2 = 0; g2 < ngrp; g2 += 2) {
+                LOAD_Q(gb, ebase, g2 + 1)
+                WALK_Q4(ga, rec, g2, ebase)
+                if (g2 + 2 < ngrp) {
+                    LOAD_Q(ga, ebase, g2 + 2)
+                } else if (blk + 1 < nblk) {
+                    LOAD_Q(ga, ebase + WAVE, 0)
+                }
+                WALK_Q4(gb, rec, g2 + 1, ebase)
+            }
+            rec = nxt;
+        }
+#undef LOAD_Q
+#undef WALK_Q4
+        flush4(false);
+        return;
+    }
+    // the walk of the full-width and fixed-point instantiations: one entry per step
     auto flush = [&](bool lower_half_only) {
         if (cur_xy != PAD_XY) {
-            acc_t f0 = acc0, f1 = acc1;                       // what the lane adds (GZ: acc0 itself stays: it may be carried)
-            if (GZ) {
-                // the cell's 64 sums A[hx][row][j] (one per lane) -> lane (hx, c): sum_j W1[j][c] A[hx][row][j] for rows 0 and 1,
-                // through the wave's 256 bytes of LDS (a half-wave reads ONE address: broadcast) and the slice's row c
-                gz_as[lane] = (float)acc0;
-                WAVE_SYNC();
-                const float4_t* const A = (const float4_t*)(gz_as + hx * 32);
-                // (the slice's row is read anew in every flush: as a loop invariant the compiler keeps its 16 values in registers -
-                // 86 VGPRs, 5 waves per SIMD - so the row's offset is made opaque to it)
-                unsigned wrow = (unsigned)(c * GZ_WP);
-                asm volatile("" : "+v"(wrow));
-                const float4_t* const Wc = (const float4_t*)(gz_w + wrow);
-                float r0 = 0.0f, r1 = 0.0f;
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const float4_t a0 = A[jj], a1 = A[4 + jj], wv = Wc[jj];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { r0 += wv[i] * a0[i]; r1 += wv[i] * a1[i]; }
-                    // two halves of six reads, each summed where it stands: all twelve in flight (the compiler moves the sums behind
-                    // the lower-half-only flush's lane test) take 48 registers - 86 VGPRs in all, 5 waves per SIMD
-                    if (jj & 1) asm volatile("" : "+v"(r0), "+v"(r1));
-                }
-                WAVE_SYNC();                                  // (the next flush's write stays behind these reads)
-                f0 = (acc_t)r0;
-                f1 = (acc_t)r1;
-            }
+            const acc_t f0 = acc0, f1 = acc1;
             const unsigned o0 = (cur_xy & ~3u) + lane_off + ((cur_xy & 1u) & (unsigned)hx) * dm_bytes;
             const unsigned o1 = o0 + ((cur_xy >> 1) & 1u) * dM_bytes;
             if (DET) {
@@ -447,7 +569,7 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
         Rec r;
         const int e = e0 + blk * WAVE + lane;
         r.xy = sxy[e];
-        r.row = sgrow[e] * (GZ ? 64 : 512);
+        r.row = sgrow[e] * 512;
         unsigned prev = __shfl_up(r.xy, 1, WAVE);
         if (lane == 0) prev = prev_last;
         const bool fresh = r.xy != prev;
@@ -458,12 +580,11 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     };
     constexpr int WALK_N = 8;      // entries per load-ahead group (2 groups in flight: 2*WALK_N VGPRs)
     const float2_t* const wlane = (const float2_t*)sw + hx;                    // + 2 * entry
-    const float* const wlane1 = (const float*)sw + (lane >> 4);                // GZ: the lane's own weight 2 hx + row, + 4 * entry
     // A row load is TWO instructions: v_readlane of the row's byte offset into an SGPR, and a buffer load that adds that SGPR
     // (soffset) and the lane's channel offset (voffset) to the descriptor's base - the global_load form needed a VALU add
     // per entry in between, and the walk is bound by instruction issue.
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)gcol, 0, GZ ? (int)((unsigned)npts * 64u) : (int)((unsigned)npts * 512u - (unsigned)(d * 64 + lvl * 32) * 4u), 0x00020000);
-    const int cvoff = GZ ? (lane & 15) * 4 : c * 4;
+    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc((void*)gcol, 0, (int)((unsigned)npts * 512u - (unsigned)(d * 64 + lvl * 32) * 4u), 0x00020000);
+    const int cvoff = c * 4;
 #define LOAD_HALF(buf, rec, half)                                                             \
     _Pragma("unroll") for (int t = 0; t < WALK_N; ++t) {                                      \
         const int rowb = __builtin_amdgcn_readlane((rec).row, (half) * WALK_N + t);           \
@@ -472,16 +593,14 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
 #define WALK_HALF(buf, rec, half, ebase)                                                      \
     _Pragma("unroll") for (int t = 0; t < WALK_N; ++t) {                                      \
         const int idx = (half) * WALK_N + t;                                                  \
-        float2_t w2 = {0.f, 0.f};                                                             \
-        if (GZ) w2[0] = wlane1[4 * ((ebase) + idx)];                                          \
-        else w2 = wlane[2 * ((ebase) + idx)];                                                 \
+        const float2_t w2 = wlane[2 * ((ebase) + idx)];                                       \
         if (((idx < 32 ? fresh_lo : fresh_hi) >> (idx & 31)) & 1u) {     /* one s_bitcmp on a 32-bit scalar */ \
             if (((idx < 32 ? adj_lo : adj_hi) >> (idx & 31)) & 1u) {                          \
                 /* next cell along the minor axis: its first texel column is our second one - keep those sums */ \
                 flush(true);                                                                  \
                 const acc_t s0 = __shfl_xor(acc0, 32, WAVE), s1 = __shfl_xor(acc1, 32, WAVE); \
                 acc0 = hx ? (acc_t)0 : s0;                                                    \
-                acc1 = (hx || GZ) ? (acc_t)0 : s1;                                            \
+                acc1 = hx ? (acc_t)0 : s1;                                                    \
                 if (DET) {            /* det_bad travels with the carried column's sums and with nothing else */ \
                     const int carried_bad = __shfl_xor((int)det_bad, 32, WAVE);               \
                     det_bad = !hx && carried_bad;                                             \
@@ -500,8 +619,6 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
             det_bad = det_bad || !(fabsf(t0_) < FIX_LIMIT) || !(fabsf(t1_) < FIX_LIMIT);      \
             acc0 += (acc_t)__float2ll_rn(t0_ * FIX_SCALE);                                    \
             acc1 += (acc_t)__float2ll_rn(t1_ * FIX_SCALE);                                    \
-        } else if (GZ) {                                                                      \
-            acc0 += (acc_t)(g * w2[0]);                                                       \
         } else {                                                                              \
             acc0 += (acc_t)(g * w2[0]);                                                       \
             acc1 += (acc_t)(g * w2[1]);                                                       \
