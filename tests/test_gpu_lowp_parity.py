@@ -219,3 +219,38 @@ def test_exact_arithmetic_inputs_match_the_plain_oracle(R, S):
         print(f"exact {R}x{S} {name}: max-normalised error {err:.2e}, element-wise worst / bar {info[1]:.2e}")
         assert err <= OUT_RTOL, (name, err)
         assert ok, (name, info)
+
+
+# ---- the round-1 wrapper ----------------------------------------------------------------------------------------------------
+def test_round1_wrapper_has_the_bits_of_the_general_entry():
+    """eslam_render_fwd_lowp (descriptors whose `data` is the half copy) against eslam_render_fwd given the same half copies through
+    data_f16, on 64 rays: the three outputs bit for bit - and not the float32 kernel's."""
+    import ctypes
+    from myslam_amd import _hip, harness, lowp, ops
+    from tests.test_gpu_parity import _dev
+    dev = _dev()
+    wl = harness.Workload("room0", 256, 24, 8, dev, planes="synth", state="trained")
+    R, S = 64, 32
+    assert wl.R >= R
+    with torch.no_grad():
+        z = wl.forward()[3][:R].contiguous()
+    ro, rd = wl.rays_o.detach()[:R].contiguous(), wl.rays_d.detach()[:R].contiguous()
+    half = lowp.HalfPlanes(wl.planes)
+    masters = [p.detach() for p in wl.plane_list]
+    arr16, _k16 = _hip.make_planes(half.flat, dtype=torch.float16)
+    arr_mixed, _km = _hip.make_planes(masters, half=half.flat)
+    arr_f32, _kf = _hip.make_planes(masters)
+    dec, _kd = _hip.make_decoders(ops.decoder_params(wl.decoders), ops.beta_tensor(wl.decoders.beta, dev))
+    bound, st, p, lib = _hip.make_bound(wl.renderer._bound6), _hip.stream_handle(dev), _hip.ptr, _hip.lib()
+    new = lambda: (torch.full((R,), -7.25, device=dev), torch.full((R, 3), -7.25, device=dev), torch.full((R, S), -7.25, device=dev))
+    a, b, c = new(), new(), new()
+    _hip.check(lib.eslam_render_fwd_lowp(arr16, ctypes.byref(dec), bound, p(ro), p(rd), p(z), R, S, p(a[0]), p(a[1]), p(a[2]), st),
+               "eslam_render_fwd_lowp")
+    for arr, o in ((arr_mixed, b), (arr_f32, c)):
+        _hip.check(lib.eslam_render_fwd(arr, ctypes.byref(dec), bound, p(ro), p(rd), p(z), R, S, p(o[0]), p(o[1]), p(o[2]), None, None, None,
+                                        None, st), "eslam_render_fwd")
+    torch.cuda.synchronize()
+    for name, x, y, w in zip(("depth", "rgb", "sdf"), a, b, c):
+        assert bool(torch.isfinite(x).all()) and not bool((x == -7.25).any()), name
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32)), (name, int((x != y).sum()))
+        assert 0 < hp.rel_err(_np(x), _np(w)) < 1e-2, (name, "the wrapper ran the float32 kernel, or something else")
