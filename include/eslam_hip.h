@@ -747,6 +747,21 @@ int eslam_scatter_bundle_samples(int64_t n, int S, int render);
  * Host bookkeeping, no launch.  FOR TESTS ONLY: one unsynchronised process-wide value written at dispatch - with concurrent
  * callers it is racy and names only the last dispatch; no caller may branch on it. */
 int eslam_last_backward_rank16(void);
+/* The rank-16 scatter's paired grid: where the SDF decoder's plane and the colour decoder's of one (orientation, level) -
+ * planes p and p + 6 - agree in width, height and strides and both receive gradients, one workgroup per bundle sorts the
+ * bundle's cells once and walks them twice; the other planes keep a workgroup each (the reference's default shapes agree at the
+ * coarse level only: three pairs, six single planes).  With no agreeing pair the 12-plane grid is used.
+ * eslam_scatter_pairing(mode): 0 = never, 1 = auto (the default: pair when bundles x (12 - pairs) >= 3 x the device's compute
+ * units - smaller batches want more workgroups, not fewer), 2 = whenever a pair agrees; returns the previous mode, an invalid
+ * mode changes nothing.  A process-wide host-side value read at launch - FOR TESTS AND MEASUREMENTS, set it while no other
+ * thread launches.
+ * eslam_last_scatter_paired(): 1 if the last scatter launch of this process used the paired grid.  Host bookkeeping, FOR TESTS
+ * ONLY, racy with concurrent callers like eslam_last_backward_rank16.
+ * eslam_scatter_pairs_auto(n, S, cus, npairs): what the auto rule decides for n rays of S samples, npairs (1..6) of whose plane
+ * pairs agree, on a device of `cus` compute units.  Host arithmetic only, no launch. */
+int eslam_scatter_pairing(int mode);
+int eslam_last_scatter_paired(void);
+int eslam_scatter_pairs_auto(int64_t n, int S, int cus, int npairs);
 /* The same kind of bookkeeping, FOR TESTS ONLY: 1 = that backward read the forward pass's saved first hidden layer
  * (eslam_render_bwd_h / _bwd_loss_h with a buffer, float32 planes), 0 = it recomputed the layer from the features. */
 int eslam_last_backward_saved_hidden(void);

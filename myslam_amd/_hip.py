@@ -161,6 +161,9 @@ SIGNATURES = {
     "eslam_deterministic": (_i, []),
     "eslam_scatter_bundle_samples": (_i, [_i64, _i, _i]),
     "eslam_last_backward_rank16": (_i, []),
+    "eslam_scatter_pairing": (_i, [_i]),
+    "eslam_last_scatter_paired": (_i, []),
+    "eslam_scatter_pairs_auto": (_i, [_i64, _i, _i, _i]),
     "eslam_last_backward_saved_hidden": (_i, []),
     "eslam_loss_scratch_floats": (_i64, [_i64]),
     "eslam_loss_scratch_reset": (_i, [_vp, _i64, _vp]),

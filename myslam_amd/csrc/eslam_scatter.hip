@@ -73,8 +73,18 @@ struct ShadowOff { int64_t o[NPL]; };
 //   states what is computed, tests/quad_walk_ref.py restates the walk's bookkeeping in numpy.
 constexpr int SC_NT = 512;
 constexpr int GZ_WP = 20;                           // pitch (floats) of the W1 slice's rows [c][j]: 16-byte aligned, conflict-free
-template <bool RENDER, bool DET, int SPT = 4, bool GZ = false>
-__global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet planes, const Bound bnd,
+// PAIR (rank-16 path): a workgroup may serve the two planes pi and pi + 6 of one (orientation, level) - the SDF decoder's and the
+//   colour decoder's.  They bundle the same rays, and where they agree in resolution and strides (the host checks it pair by
+//   pair: the reference's default colour planes are twice as fine at the fine level, so only the coarse pairs agree there) cells,
+//   bounding box, sort and the sorted records are the same entry for entry: phases (1) and (2) run once and the walk runs twice
+//   over the records that are still in LDS, per pass with the decoder's half of gz, its gradient plane and its slice of W1
+//   (restaged between the passes: both slices do not fit beside the records at three workgroups per CU).  The grid runs over a
+//   work list per bundle instead of the 12 planes: the planes left single in front (the fine planes: most cells, most flushes,
+//   the longest workgroups), the agreeing pairs (two short walks over few cells) behind them, where they fill the grid's tail.  The
+//   list arrives in `shoff`, which only the fixed-point instantiations use otherwise: o[w] = plane | walks << 4, and its length
+//   in o[0] << 8.
+template <bool RENDER, bool DET, int SPT = 4, bool GZ = false, bool PAIR = false>
+__global__ __launch_bounds__(SC_NT) __attribute__((amdgpu_waves_per_eu(PAIR ? (SPT == 4 ? 6 : 8) : 2))) void scatter_sort_kernel(const PlaneSet planes, const Bound bnd,
                                                           const float* __restrict__ rays_o,
                                                           const float* __restrict__ rays_d,
                                                           const float* __restrict__ z_vals,     // RENDER ? [R,S] : pts [N,3]
@@ -85,6 +95,8 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
                                                           const float* __restrict__ gz_w1_sdf, const float* __restrict__ gz_w1_rgb) {
     constexpr int NT = SC_NT;
     static_assert(!GZ || (RENDER && !DET), "GZ: the float render path only");
+    static_assert(!PAIR || GZ, "PAIR: the rank-16 path only");
+    const int NPLW = PAIR ? (int)(shoff.o[0] >> 8) : NPL;   // planes (PAIR: entries of the work list) the grid runs over
     constexpr int BM = SPT * NT;                       // SPT samples per thread in the cell / sort phases
     constexpr int CH = WAVE * SPT;                     // sorted entries a wave walks
     static_assert(SPT == 2 || SPT == 4, "samples per thread");
@@ -152,8 +164,14 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
     }
     int bidx, pi;
     if (plane_major) { bidx = bid % nbundles; pi = bid / nbundles; }
-    else { pi = bid % NPL; bidx = bid / NPL; }
-    if (bidx >= nbundles || pi >= NPL) return;
+    else { pi = bid % NPLW; bidx = bid / NPLW; }
+    if (bidx >= nbundles || pi >= NPLW) return;
+    int npass = 1;
+    if constexpr (PAIR) {
+        const int item = (int)shoff.o[pi] & 0xFF;
+        pi = item & 15;
+        npass = item >> 4;
+    }
     const int d = pi / 6, o = (pi % 6) >> 1, lvl = pi & 1;
     const eslam_plane_t& P = planes.p[pi];
     // GZ: thread (j, c) fetches W1[j][lvl * 32 + c] of the plane's decoder now and stores it behind the cell phase's own loads
@@ -406,11 +424,32 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
         //   more LDS round trips, 12-13 us in all: DESIGN.md section 5 "Four entries per step".)
         // (the lane-derived addresses of the walk are formed HERE: derived from `lane` itself the compiler forms them at the kernel's
         // start and keeps them through the cell and sort phases, whose registers are the kernel's peak)
+        // PAIR, two walks: the second decoder's element of the slice, fetched now (behind the sort, whose registers are the kernel's peak)
+        // and stored between the passes
+        // (its addresses come from an opaque copy of the thread number: shared with the first slice's, formed at the kernel's
+        // start, they would be kept through the sort)
+        float gz_wv2 = 0.0f;
+        unsigned wt = threadIdx.x;
+        if constexpr (PAIR) {
+            asm volatile("" : "+v"(wt));
+            if (npass > 1) gz_wv2 = gz_w1_rgb[(wt >> 5) * ESLAM_FEAT + lvl * ESLAM_C_DIM + (wt & 31)];
+        }
         int wl = lane;
+        // PAIR: the walk runs once per decoder over the same records.  The loop stays rolled: the walk's body is most of the
+        // kernel's code and has to fit the instruction cache once.  (wl is made opaque INSIDE the loop: the lane-derived
+        // addresses are formed anew in each pass, not kept as loop invariants)
+#pragma nounroll
+        for (int pass = 0; pass < (PAIR ? npass : 1); ++pass) {
         asm volatile("" : "+v"(wl));
         const int s = wl >> 4, whx = wl >> 5, wc = wl & 31;    // accumulating role (s, j); flushing role (hx, c)
         const unsigned wlane_off = (unsigned)(wc * psc) << 2;
         const int up1 = ((wl + WAVE - 1) & (WAVE - 1)) << 2;         // ds_bpermute address of the lane below
+        if constexpr (PAIR) {
+            gcol = (const char*)(g_feat + (size_t)(d + pass) * (size_t)npts * 16);
+            gbytes = (char*)planes.p[pi + pass * (NPL / 2)].grad;
+            cur_xy = PAD_XY;
+            last_xy = PAD_XY;
+        }
         float2_t alo = {0.f, 0.f}, ahi = {0.f, 0.f};             // k = 0, 1 (hx = 0: rows 0, 1) and k = 2, 3 (hx = 1)
         // Flush of a finished cell.  The slots' partial sums are added by a transposing exchange - lane bit 4, then lane bit 5 -
         // after which lane (s, j) holds the cell's sum for k = s: the layout gz_as[k * 16 + j] the expansion reads.  Then lane
@@ -511,6 +550,16 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
         float ga[WALK_Q], gb[WALK_Q];
         Rec4 rec = fetch4(0, PAD_XY);
         LOAD_Q(ga, e0, 0)
+        if constexpr (PAIR) {
+            // the second pass reads the colour decoder's slice: every wave has left the first pass's last flush before it is
+            // replaced (the pass's first record block and row loads are already under way)
+            if (pass == 1) {
+                __syncthreads();
+                asm volatile("" : "+v"(wt));
+                gz_w[(wt & 31) * GZ_WP + (wt >> 5)] = gz_wv2;
+                __syncthreads();
+            }
+        }
 #pragma unroll 1
         for (int blk = 0; blk < nblk; ++blk) {
             if ((unsigned)__builtin_amdgcn_readfirstlane((int)rec.xy) == PAD_XY) break;   // sorted: everything from here is padding
@@ -535,9 +584,10 @@ __global__ __launch_bounds__(SC_NT) void scatter_sort_kernel(const PlaneSet plan
             }
             rec = nxt;
         }
+        flush4(false);
+        }
 #undef LOAD_Q
 #undef WALK_Q4
-        flush4(false);
         return;
     }
     // the walk of the full-width and fixed-point instantiations: one entry per step
@@ -736,6 +786,68 @@ bool eslam_scatter_can_reduce(bool render) {
     return render && !eslam_deterministic();
 }
 
+// The paired grid of the rank-16 path (scatter_sort_kernel<PAIR>): where the SDF decoder's plane and the colour decoder's of
+// one (orientation, level) agree in shape, one workgroup per bundle sorts once and walks twice.  Fewer workgroups, some of them
+// longer: below SC_PAIR_WGS_PER_CU workgroups per CU the kernel is latency-bound and wants more workgroups, not fewer.
+#define SC_PAIR_WGS_PER_CU 3
+static int g_scatter_pairing = 1;                     // 0 never, 1 auto, 2 whenever a pair of planes allows it
+static int g_last_scatter_paired = 0;
+
+extern "C" int eslam_scatter_pairing(int mode) {
+    const int prev = g_scatter_pairing;
+    if (mode >= 0 && mode <= 2) g_scatter_pairing = mode;
+    return prev;
+}
+
+extern "C" int eslam_last_scatter_paired(void) { return g_last_scatter_paired; }
+
+// the auto rule: whether a render batch of n rays x S samples, npairs of whose six plane pairs agree, is paired on a device of
+// `cus` compute units
+extern "C" int eslam_scatter_pairs_auto(int64_t n, int S, int cus, int npairs) {
+    if (n <= 0 || S <= 0 || S > 256 || cus <= 0 || npairs <= 0 || npairs > NPL / 2) return 0;
+    int bm = 0;
+    const int bundle = scatter_bundle_size(S, (int)n, &bm);
+    const int64_t nbundles = (n + bundle - 1) / bundle;
+    return nbundles * (NPL - npairs) >= (int64_t)SC_PAIR_WGS_PER_CU * cus;
+}
+
+// The work list of a bundle (PAIR in the kernel's header comment) into so.o: the planes that stay single in plane order, then
+// the pairs p, p + 6 that can share a workgroup - same cells, same offsets, both with a gradient.  Returns the number of pairs.
+// The order is measured (4096 x 64, shipped shapes: three coarse pairs, six fine planes; scatter_sort_kernel in the replayed step,
+// profiles/r10/list_orders.txt): pairs first 85 - 89 us against the 12-plane grid's 79 - 83, pairs last 70 - 72.  A plane-major grid
+// then starts with the fine planes' long workgroups and ends with the short ones; the same order WITHOUT pairing (twelve
+// single planes, fine ones first) gives 72 - 77.
+static int scatter_work_list(const eslam_plane_t* planes, ShadowOff* so) {
+    bool pair[NPL / 2];
+    int n = 0, npairs = 0;
+    for (int p = 0; p < NPL / 2; ++p) {
+        const eslam_plane_t &a = planes[p], &b = planes[p + NPL / 2];
+        pair[p] = a.w == b.w && a.h == b.h && a.stride_x == b.stride_x && a.stride_y == b.stride_y &&
+                  a.stride_c == b.stride_c && a.grad && b.grad;
+        if (pair[p]) ++npairs;
+    }
+    for (int pi = 0; pi < NPL; ++pi)
+        if (!pair[pi % (NPL / 2)]) so->o[n++] = pi | (1 << 4);
+    for (int p = 0; p < NPL / 2; ++p)
+        if (pair[p]) so->o[n++] = p | (2 << 4);
+    so->o[0] |= (int64_t)n << 8;
+    return npairs;
+}
+
+// compute units of the current device (0: unknown - the auto rule then does not pair)
+static int scatter_device_cus() {
+    constexpr int MAXDEV = 64;
+    static int cus[MAXDEV];
+    int devi = 0;
+    if (hipGetDevice(&devi) != hipSuccess || devi < 0 || devi >= MAXDEV) return 0;
+    if (cus[devi] == 0) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, devi) != hipSuccess || n <= 0) return 0;
+        cus[devi] = n;
+    }
+    return cus[devi];
+}
+
 int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float* rays_o, const float* rays_d,
                      const float* z_or_pts, int64_t R, int S, bool render, const float* g_feat, const int* perm,
                      hipStream_t st, const DecReduceArgs* red, const eslam_decoders_t* gz_dec) {
@@ -782,7 +894,14 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
             return 1;
         }
     const int nbundles = (nunits + bundle - 1) / bundle;
-    dim3 grid(nbundles * NPL);
+    // pairing is decided after the bundle size (scatter_sort_kernel<PAIR>; the rule: SC_PAIR_WGS_PER_CU)
+    ShadowOff work = {};
+    int npairs = 0;
+    if (gz_dec && g_scatter_pairing != 0) npairs = scatter_work_list(planes, &work);
+    const bool paired = npairs > 0 && (g_scatter_pairing == 2 || (int64_t)nbundles * (NPL - npairs) >=
+                                                                     (int64_t)SC_PAIR_WGS_PER_CU * scatter_device_cus());
+    g_last_scatter_paired = paired ? 1 : 0;
+    dim3 grid(nbundles * (paired ? NPL - npairs : NPL));
     DecReduceArgs red_args = {};
     int red_blocks = 0;
     if (red) {
@@ -796,7 +915,7 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
     }
 #define LAUNCH_SC(RD, PERM, SS, ...)                                                                                      \
     hipLaunchKernelGGL((scatter_sort_kernel<RD, false, ##__VA_ARGS__>), grid, dim3(SC_NT), 0, st, ps, bnd, rays_o, rays_d, z_or_pts, \
-                       PERM, (int)R, SS, g_feat, bundle, nbundles, (long long*)nullptr, ShadowOff{}, red_args, red_blocks, \
+                       PERM, (int)R, SS, g_feat, bundle, nbundles, (long long*)nullptr, work, red_args, red_blocks, \
                        gz_dec ? gz_dec->w1 : nullptr, gz_dec ? gz_dec->cw1 : nullptr)
     if (eslam_deterministic()) {
         // fixed-point scatter into the int64 shadow, then shadow -> float gradients (DET in the kernel's header comment)
@@ -860,7 +979,10 @@ int eslam_scatter_v2(const eslam_plane_t* planes, const Bound& bnd, const float*
         }
         return eslam_check_launch("scatter_fixed_to_float_kernel");
     }
-    if (gz_dec) {
+    if (gz_dec && paired) {
+        if (bm == 1024) LAUNCH_SC(true, perm, S, 2, true, true);
+        else LAUNCH_SC(true, perm, S, 4, true, true);
+    } else if (gz_dec) {
         if (bm == 1024) LAUNCH_SC(true, perm, S, 2, true);
         else LAUNCH_SC(true, perm, S, 4, true);
     } else if (render) {
