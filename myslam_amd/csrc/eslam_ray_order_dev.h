@@ -1,6 +1,6 @@
-// The ray ordering and the gradient clear as device functions: the bodies of ray_order_kernel (eslam_scatter.hip) and of the
+// The ray ordering and the gradient clear as device functions: the bodies of ray_order_kernel (eslam_ray_order.hip) and of the
 // ordering / clear roles of step_front_kernel (eslam_sample.hip).  The two files are compiled with different -ffp-contract
-// settings, so the ordering pins its own (contraction ON, as eslam_scatter.hip has always compiled it): its keys and the fan
+// settings, so the ordering pins its own (contraction ON, as ray_order_kernel has always been compiled): its keys and the fan
 // extents come out the same from either file.
 #pragma once
 #include "eslam_common.h"

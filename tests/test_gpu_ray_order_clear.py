@@ -15,7 +15,7 @@ import torch
 from tests import helpers as hp
 
 pytestmark = pytest.mark.gpu
-CHUNK = 8192                         # rays ordered by one workgroup (SORT_MAX in csrc/eslam_scatter.hip)
+CHUNK = 8192                         # rays ordered by one workgroup (SORT_MAX in csrc/eslam_ray_order_dev.h)
 NAN_BITS = 0x7FC00123                # a quiet NaN with a payload: what an uncleared gradient buffer is filled with here
 PLANES = [(0, 1), (0, 2), (1, 2)]    # axes of orientation 0 (xy), 1 (xz), 2 (yz)
 

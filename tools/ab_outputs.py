@@ -1,5 +1,6 @@
 """A/B check of two builds of the library on identical inputs: dump outputs + gradients of a list of configurations
-(python tools/ab_outputs.py dump out.npz, once per build via ESLAM_HIP_LIB), then `compare a.npz b.npz`."""
+(python tools/ab_outputs.py dump out.npz, once per build via ESLAM_HIP_LIB), then `compare a.npz b.npz` (relative difference
+beyond 1e-5) or `compare a.npz b.npz exact` (every array whose bytes differ: what two ESLAM_DETERMINISTIC=1 dumps must not have)."""
 import sys, os, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CONFIGS = [("toy", 999, 32, 8, 0.0), ("toy", 497, 32, 8, 0.0), ("toy", 333, 32, 8, 0.1), ("toy", 1000, 16, 8, 0.0),
@@ -32,9 +33,14 @@ if sys.argv[1] == "dump":
     np.savez(sys.argv[2], **out)
 else:
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
+    exact = len(sys.argv) > 4 and sys.argv[4] == "exact"
     for k in a.files:
         x, y = a[k], b[k]
+        if exact:
+            if x.shape != y.shape or x.tobytes() != y.tobytes():
+                print("BYTES DIFFER", k, CONFIGS[int(k.split('_')[0])], int((x != y).sum()) if x.shape == y.shape else "shape", "elements")
+            continue
         err = float(np.abs(x - y).max() / (np.abs(y).max() + 1e-30))
         if err > 1e-5:
             print("DIFF", k, CONFIGS[int(k.split('_')[0])], err)
-    print("compared", len(a.files), "arrays")
+    print("compared", len(a.files), "arrays", "(exact)" if exact else "")
