@@ -13,16 +13,17 @@ def _np(t):
     return None if t is None else t.detach().float().cpu().numpy()
 
 
-def step(fx, form, grad_o=True, grad_d=True, ray_grads=True):
+def step(fx, form, grad_o=True, grad_d=True, ray_grads=True, dec_grad=None):
     """form: "tracking" = planes and decoders frozen, losses.tracking_loss; "separate" / "fused" = a mapping step with the
     loss formed outside / inside the kernels, planes and decoders trained.  grad_o / grad_d: which of rays_o / rays_d require
-    grad.  Returns numpy arrays: depth, color, sdf, z, feat (the saved bf16 features), g_o, g_d (None where not asked for),
+    grad.  dec_grad=False: a mapping step with the decoders frozen (their gradients come back as None).
+    Returns numpy arrays: depth, color, sdf, z, feat (the saved bf16 features), g_o, g_d (None where not asked for),
     and for a mapping step planes (12), dec {name}, beta."""
     from myslam_amd import lowp, losses, ops
     from tests.test_gpu_parity import _dev, build
     dev = _dev()
     train = form != "tracking"
-    sc, planes, dec, renderer = build(fx, planes_grad=train, dec_grad=train)
+    sc, planes, dec, renderer = build(fx, planes_grad=train, dec_grad=train if dec_grad is None else dec_grad)
     rand = tuple(None if t is None else t.to(dev) for t in hp.rand_inputs(fx))
     ro = torch.from_numpy(fx["rays_o"]).to(dev).requires_grad_(grad_o)
     rd = torch.from_numpy(fx["rays_d"]).to(dev).requires_grad_(grad_d)

@@ -22,6 +22,7 @@ CASES = {
     "ray_gradients": dict(rays_grad=True),
     "nchw": dict(channels_last=False),
     "masked_and_depthless": dict(mask=True, zero_frac=0.1),
+    "frozen_separate_5x72": dict(R=5, ns=64, loss="separate", frozen=True),
 }
 
 

@@ -97,6 +97,25 @@ def test_mapping_ray_gradients_against_the_model(case, form):
     assert np.array_equal(only_o["g_o"], r["g_o"]) and np.array_equal(only_d["g_d"], r["g_d"])
 
 
+def test_fused_mapping_step_with_frozen_decoders():
+    """mlp_bwd_kernel<2, false, LOWP>, which no other test reaches: the loss formed inside the kernels, planes trained, decoders
+    frozen (g_dec NULL: no weight-gradient contractions), rays taking gradients.  The ray gradients are held to the model like
+    those of the trained step, and are its bits: everything in front of the coordinate kernel is the same arithmetic with or
+    without the contractions and has no atomics."""
+    case = MAPPING_CASES[0]
+    fx, first, model = _mapping_model(case)
+    full = pg.step(fx, "fused")
+    r = pg.step(fx, "fused", dec_grad=False)
+    assert all(g is None for g in r["dec"].values())
+    for k in ("depth", "color", "sdf", "z", "feat"):
+        assert np.array_equal(r[k], first[k]), k
+    _hold(f"{case} fused, frozen decoders", (r["g_o"], r["g_d"]), model)
+    assert np.array_equal(r["g_o"], full["g_o"]) and np.array_equal(r["g_d"], full["g_d"])
+    assert all(np.isfinite(p).all() and np.abs(p).max() > 0 for p in r["planes"])
+    for a, b in zip(r["planes"], full["planes"]):      # float atomics: order-dependent rounding (tests/test_gpu_determinism.py)
+        assert hp.rel_err(a, b) <= 1e-5
+
+
 def test_ray_gradients_leave_plane_and_decoder_gradients_bit_equal():
     """Plane and decoder gradients of a mapping step with ray gradients are the BITS of the same step without: the coordinate
     kernel runs behind the scatter and writes nothing but g_rays_o / g_rays_d.  Compared in a child process under

@@ -374,6 +374,44 @@ def test_decoders_forward_and_backward():
     assert hp.rel_err(sdf.cpu().numpy(), fx["raw"][:, 3]) <= RTOL
 
 
+def test_decoders_backward_with_frozen_decoders():
+    """The free-point backward without weight gradients (mlp_bwd_kernel<0, false, ...>, g_dec NULL) on 70 points - two tiles, the
+    second with 6 points: point and plane gradients against oracle autograd, as in test_decoders_forward_and_backward."""
+    from myslam_amd import scene as scn
+    from myslam_amd.src.networks.decoders import Decoders
+    from oracle import eslam_oracle as orc
+    dev = _dev()
+    fx = hp.load("decoders_room0_points")
+    n = 70
+    sc = scn.make_scene("room0")
+    planes = scn.synth_planes(sc, device=dev)
+    planes = tuple([p.requires_grad_(True) for p in grp] for grp in planes)
+    dec = Decoders()
+    dec.load_state_dict({k[6:]: torch.from_numpy(fx[k]) for k in fx.files if k.startswith("param:")})
+    dec = dec.to(dev)
+    dec.bound = sc.bound
+    for t in dec.parameters():
+        t.requires_grad_(False)
+    p = torch.from_numpy(fx["points"][:n]).to(dev).requires_grad_(True)
+    raw = dec(p, all_planes=planes)
+    assert raw.shape == (n, 4)
+    assert hp.rel_err(raw.detach().cpu().numpy(), fx["raw"][:n]) <= RTOL
+    wts = torch.linspace(0.5, 1.5, raw.numel(), device=dev).reshape(raw.shape)
+    (raw * wts).sum().backward()
+    assert all(t.grad is None for t in dec.parameters())
+    cp = scn.synth_planes(sc, dtype=torch.float64, channels_last=False)
+    cp = tuple([q.requires_grad_(True) for q in grp] for grp in cp)
+    params = hp.params_from(fx, dtype=torch.float64, requires_grad=False)
+    p64 = torch.from_numpy(fx["points"][:n]).double().requires_grad_(True)
+    raw64 = orc.decode(p64, cp, params, sc.bound.double())
+    (raw64 * wts.cpu().double()).sum().backward()
+    assert np.abs(p64.grad.numpy()).max() > 0
+    assert hp.rel_err(p.grad.cpu().numpy(), p64.grad.numpy()) <= RTOL
+    for a, b in zip(hp.flat_planes(planes), hp.flat_planes(cp)):
+        assert np.abs(b.grad.numpy()).max() > 0
+        assert hp.rel_err(a.grad.cpu().numpy(), b.grad.numpy()) <= RTOL
+
+
 def _bench_like(R, n_strat, n_imp, scene="room0", zero_frac=0.0, seed=0):
     from myslam_amd import harness
     return harness.make_workload(scene, R, n_strat, n_imp, device=_dev(), zero_frac=zero_frac, seed=seed)

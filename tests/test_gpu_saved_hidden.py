@@ -5,7 +5,7 @@ Layer 1 of the backward was the same instructions on the same values as in the f
 no bit: depth / rgb / sdf, every decoder gradient, the beta gradient and - where the rays take gradients - g_rays_o and g_rays_d
 must be torch.equal between the two paths.  Plane gradients go through unordered float atomics: they are held to the rule of
 tests/test_gpu_rank16_scatter.py, max(1e-5, 4 x) max-normalised, x = what two runs of the recompute path differ by among
-themselves, measured here; in deterministic mode (a child process, all ten cases) they must agree bit for bit too.
+themselves, measured here; in deterministic mode (a child process, every case) they must agree bit for bit too.
 
 The loss VALUE is the one quantity neither path reproduces to the bit outside deterministic mode: the forward pass (and
 eslam_loss_value) adds its workgroups' partial sums with unordered float atomics (loss_finalize), whichever way the backward
@@ -27,6 +27,8 @@ of the first.
    8  ray_gradients         full-width rows and coord_bwd_kernel
    9  nchw                  the strided forward kernel stores the layer
   10  masked_and_depthless  a third of the rays masked out, 10 % without depth
+  11  frozen_separate_5x72  MODE 1 with WGRAD = false, which no other case reaches (here on the rank-16 pair, in the deterministic
+                            child on full-width rows); R = 5, S = 64 + 8: two chunks, the second of one half-valid block
 Cases 1, 6 and 8 run through both host glues.  Every case is also held to the oracle, with the criteria of
 tests/test_gpu_parity.py (tests/helpers.py: outputs and loss within 1e-4 of the float64 oracle, plane gradients by
 plane_grads_close, decoder gradients against the float32 and float64 oracles with the ambiguous-sample slack, ray gradients as

@@ -58,7 +58,9 @@ r = wl.renderer
 gt = torch.full((r.H, r.W), 1.5, device=dev)
 c2w = wl.c2w.to(dev)
 def img():
-    r.render_img(wl.planes, wl.decoders, c2w, wl.truncation, dev, gt_depth=gt)
+    # (detached planes, frozen decoders: a call that could be back-propagated saves its first hidden layer, and for the 816000
+    # rays of the one-chunk call below the library refuses to)
+    r.render_img(planes, wl.decoders, c2w, wl.truncation, dev, gt_depth=gt)
 t = timed(img, n=5, warm=2)
 print(f"render_img {r.H}x{r.W} x {wl.S} samples: {t:.1f} ms  ({r.H*r.W*wl.S/t*1e3:.3e} ray.samples/s)")
 r.ray_batch_size = 10 ** 9           # one chunk instead of 82
