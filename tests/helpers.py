@@ -165,11 +165,30 @@ def texels_of(p_nor, plane_shapes):
     return out
 
 
-def plane_grads_close(mine, ref32, ref64, p_nor, amb, plane_shapes, rtol=1e-4, report=None):
+def excluded_share(p_nor, amb, plane_shapes):
+    """12 floats (all_planes order): of the texels the samples p_nor [N,3] touch (texels_of), the share that plane_grads_close
+    sets aside because a ReLU-ambiguous sample (amb, bool [N]) touches them too - the part of a plane's gradient the criterion
+    never looks at.  0.0 for a plane no sample touches."""
+    out = []
+    for (_, _, h, w), t in zip((s for grp in plane_shapes for s in grp), texels_of(p_nor, plane_shapes)):
+        touched, aside = torch.zeros(h * w, dtype=torch.bool), torch.zeros(h * w, dtype=torch.bool)
+        touched[t.reshape(-1)] = True
+        aside[t[amb].reshape(-1)] = True
+        out.append(float((touched & aside).sum()) / max(1, int(touched.sum())))
+    return out
+
+
+def plane_grads_close(mine, ref32, ref64, p_nor, amb, plane_shapes, rtol=1e-4, report=None, max_excluded=None):
     """Plane gradients (12 arrays [1,C,h,w], all_planes order) against the float32 oracle (comparator) with the float64 one
     as the conditioning bound, excluding the texels touched by ReLU-ambiguous samples (ambiguous_samples).  Returns
-    (ok, message).  report: a list that receives (plane, value / bar) - the larger of the two ratios - per plane looked at."""
+    (ok, message).  report: a list that receives (plane, value / bar) - the larger of the two ratios - per plane looked at.
+    max_excluded: when given, the largest share of a plane's touched texels the exclusion may remove (excluded_share); a
+    plane that loses more fails.  0.0 asks for a batch without ambiguous samples: every touched texel is compared."""
     tex = texels_of(p_nor, plane_shapes)
+    if max_excluded is not None:
+        for k, share in enumerate(excluded_share(p_nor, amb, plane_shapes)):
+            if share > max_excluded:
+                return False, f"plane {k}: {share:.2f} of its touched texels set aside as ambiguous (at most {max_excluded:.2f})"
     for k, (a, r32, r64) in enumerate(zip(mine, ref32, ref64)):
         a, r32, r64 = (np.asarray(t, dtype=np.float64).reshape(a.shape[1], -1) for t in (a, r32, r64))
         keep = np.ones(a.shape[1], dtype=bool)

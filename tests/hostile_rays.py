@@ -253,11 +253,12 @@ def ambiguous(mdl, scene, b, z):
     return pn, amb
 
 
-def accept(mine, o32, o64, pn, amb, scene, report=None, label=""):
+def accept(mine, o32, o64, pn, amb, scene, report=None, label="", max_excluded=None):
     """THE acceptance criteria of a forward + backward on this batch, as test_edge_shapes_against_oracle states them:
     outputs within RTOL of the float64 oracle; plane gradients by hp.plane_grads_close; decoder gradients against the float32
     oracle (comparator) and the float64 one (conditioning bound) with the ambiguous-sample slack; ray gradients: 97 % of the
-    rays within RTOL, the rest bounded by 0.05.  report: a dict that receives the worst value / bar per criterion."""
+    rays within RTOL, the rest bounded by 0.05.  report: a dict that receives the worst value / bar per criterion.
+    max_excluded: handed to hp.plane_grads_close (the share of a plane's touched texels the comparison may set aside)."""
     rep = {} if report is None else report
     worst = lambda k, v: rep.__setitem__(k, max(rep.get(k, 0.0), float(v)))
     for k in ("depth", "color", "sdf"):
@@ -265,7 +266,8 @@ def accept(mine, o32, o64, pn, amb, scene, report=None, label=""):
         worst("out:" + k, e / RTOL)
         assert e <= RTOL, (label, k, e)
     pr = []
-    ok, msg = hp.plane_grads_close(mine["planes"], o32["planes"], o64["planes"], pn, amb, scene.plane_shapes, RTOL, report=pr)
+    ok, msg = hp.plane_grads_close(mine["planes"], o32["planes"], o64["planes"], pn, amb, scene.plane_shapes, RTOL, report=pr,
+                                   max_excluded=max_excluded)
     if pr:
         worst("plane_grad", max(v for _, v in pr))
     assert ok, (label, msg, int(amb.sum()))

@@ -107,6 +107,7 @@ def _oracle_check(wl, R, ns, ni, bundle, label, want_paired=1):
     mdl = t16._cpu_model(wl)
     o64, o32 = (hr.oracle_step(mdl, wl.scene, b, z, cot, dt) for dt in (torch.float64, torch.float32))
     pn, amb = hr.ambiguous(mdl, wl.scene, b, z)
+    t16._print_excluded(label, pn, amb, wl.scene)
     t16._accept(mine, o32, o64, pn, amb, wl.scene, label)
     return ro, rd, z
 

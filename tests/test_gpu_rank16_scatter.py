@@ -55,7 +55,7 @@ def _assert_full_width_path(ro, rd):
     assert ro.requires_grad and rd.requires_grad and ro.grad is not None and rd.grad is not None
 
 
-def _accept(mine, o32, o64, pn, amb, scene, label):
+def _accept(mine, o32, o64, pn, amb, scene, label, max_excluded=None):
     """hostile_rays.accept (= the criteria of test_edge_shapes_against_oracle) without the ray gradients this path never has."""
     rep = {}
     for k in ("depth", "color", "sdf"):
@@ -63,7 +63,8 @@ def _accept(mine, o32, o64, pn, amb, scene, label):
         rep["out:" + k] = e / RTOL
         assert e <= RTOL, (label, k, e)
     pr = []
-    ok, msg = hp.plane_grads_close(mine["planes"], o32["planes"], o64["planes"], pn, amb, scene.plane_shapes, RTOL, report=pr)
+    ok, msg = hp.plane_grads_close(mine["planes"], o32["planes"], o64["planes"], pn, amb, scene.plane_shapes, RTOL, report=pr,
+                                   max_excluded=max_excluded)
     if pr:
         rep["plane_grad"] = max(v for _, v in pr)
     assert ok, (label, msg, int(amb.sum()))
@@ -76,6 +77,13 @@ def _accept(mine, o32, o64, pn, amb, scene, label):
         assert e64 <= max(RTOL, 1.5 * cond) + slack, (label, k, e64, cond)
     for k, v in rep.items():
         print(f"margin {label}: {k:<12s} {v:.3f}")
+
+
+def _print_excluded(label, pn, amb, scene):
+    """What the criterion leaves out here: per plane the share of the touched texels set aside with the ambiguous samples
+    (tests/test_gpu_every_texel.py runs batches where it is zero)."""
+    share = hp.excluded_share(pn, amb, scene.plane_shapes)
+    print(f"excluded {label}: {int(amb.sum())} ambiguous samples, share of touched texels not compared " + " ".join(f"{v:.2f}" for v in share))
 
 
 def _cpu_model(wl):
@@ -127,6 +135,7 @@ def test_rank16_backward_against_oracle(R, ns, ni, zero_frac, bundle, state):
     mdl = _cpu_model(wl)
     o64, o32 = (hr.oracle_step(mdl, wl.scene, b, z, cot, dt) for dt in (torch.float64, torch.float32))
     pn, amb = hr.ambiguous(mdl, wl.scene, b, z)
+    _print_excluded(f"rank16 {R}x{ns}+{ni} {state}", pn, amb, wl.scene)
     _accept(mine, o32, o64, pn, amb, wl.scene, f"rank16 {R}x{ns}+{ni} {state}")
 
 
