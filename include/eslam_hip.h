@@ -300,6 +300,24 @@ int eslam_render_bwd_loss_h(const eslam_plane_t* planes, const eslam_decoders_t*
 int eslam_decode_fwd(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
                      const float* pts, int64_t N, int flags, float* raw, float* feat, eslam_stream_t stream);
 
+/* The SDF and its gradient with respect to the point, fused: pts [N,3] world coordinates -> sdf [N] (may be NULL) and
+ * grad [N,3] = d sdf / d p.  The reference has no equivalent (its only route is autograd through Decoders.forward).
+ * sdf is what eslam_decode_fwd(ESLAM_DECODE_SDF_ONLY) writes for the same points, bit for bit (the same tile, the same
+ * operation order, no outside mask).  grad is what autograd of that sdf gives: per world axis a factor 2 / (hi - lo)
+ * (normalize_3d_coordinate, src/common.py:215-217); per plane axis of n texels a factor (n - 1) / 2, and 0 where the border
+ * clamp is active (the coordinate on or outside the bound: ATen's clip_coordinates_set_grad), so such a component is
+ * exactly 0; a ReLU's derivative is 1 where its pre-activation is > 0, else 0; a last factor 1 - sdf^2 from the tanh.
+ * flags: ESLAM_SDF_GRAD_UNIT divides every row by sqrtf(grad . grad) and writes (0, 0, 0) where grad . grad == 0.
+ * Only planes[0..5] (geometry, both levels) and the SDF decoder (w1 .. b3) are read.  Planes channels-last or the
+ * reference's NCHW, float32 only: with half copies present (data_f16) the float32 masters are read.
+ * One launch on `stream`, never synchronises, nothing per point in device memory but pts, sdf and grad; a grid of at most
+ * ESLAM_SDF_GRAD_MAX_GROUPS workgroups of 256 points walks the tiles.  N = 0 is valid and launches nothing; bad arguments
+ * (N < 0, unknown flags, a null pointer, a bad plane) come back non-zero, with eslam_last_error() set, before any launch. */
+#define ESLAM_SDF_GRAD_UNIT 1
+#define ESLAM_SDF_GRAD_MAX_GROUPS 8192
+int eslam_sdf_grad(const eslam_plane_t* planes, const eslam_decoders_t* dec, const float* bound6_host,
+                   const float* pts, int64_t N, int flags, float* sdf, float* grad, eslam_stream_t stream);
+
 /* The SDF of an implicit grid: eslam_decode_fwd(ESLAM_DECODE_SDF_ONLY | flags) on the points (xs[ix], ys[iy], zs[iz]),
  * which are never materialised.  Replaces the field half of src/utils/Mesher.py:196-217 (get_grid_uniform's points,
  * Mesher.py:178-184, through eval_points in 500k batches, then z[~mask] = -1 with the frame hull's mask).
@@ -562,6 +580,18 @@ int eslam_viewer_points(const float* points, int64_t n_points, const uint8_t* rg
 int eslam_viewer_resolve(int n_views, int H, int W, int bg_r, int bg_g, int bg_b, const void* workspace, uint8_t* image,
                          float* depth, eslam_stream_t stream);
 
+/* Headlight Lambert shading of a mesh's vertex colours for ONE view, applied before rasterisation (the reference's window is
+ * unlit; eslam_viewer_mesh and its contract are untouched: hand it `out` as the colours of that view).  verts, normals
+ * [n_verts][3] float32 (device; normals need not be unit), colors [n_verts][4] uint8 (4-byte aligned, the fourth byte
+ * ignored) or NULL = every vertex (200, 200, 200), cam_center3_host: the camera centre c (host).  Per vertex, float32
+ * operation by operation: l = c - v; nn = (nx nx + ny ny) + nz nz and ll likewise; the factor k = 1 when nn == 0 or
+ * ll == 0, else k = ambient + (1 - ambient) max(0, ((nx lx + ny ly) + nz lz) / (sqrt(nn) sqrt(ll))); every channel becomes
+ * (uint8)floor(min(255, c k) + 0.5) with c the channel's uint8 as float; alpha 255.  out [n_verts][4] uint8, 4-byte aligned.
+ * 0 <= ambient <= 1.  Zero vertices are valid and launch nothing; one launch on `stream`, never synchronises; bad arguments
+ * come back non-zero, with eslam_last_error() set, before any launch.                                                  */
+int eslam_shade_vertices(const float* verts, const float* normals, const uint8_t* colors, int64_t n_verts,
+                         const float* cam_center3_host, float ambient, uint8_t* out, eslam_stream_t stream);
+
 /* Render metrics and the frame visualiser's panel (reference src/utils/Frame_Visualizer.py:43-122): three operations on a
  * rendered frame and its ground truth.  depth, gt_depth [H][W]; color, gt_color [H][W][3]; all float32 on the device.
  * Every call launches on `stream` and never synchronises; bad arguments come back non-zero before any launch.
@@ -785,7 +815,7 @@ int eslam_loss_value(const float* depth, const float* rgb, const float* sdf, con
 /* Per-kernel device timing for bench.py's roofline line (HIP events recorded on the launch stream around each
  * kernel while enabled; adds nothing to the launch path when disabled).  Usage: enable(1); run one iteration;
  * synchronise the stream; read(ms) -> elapsed milliseconds of the LAST launch of each kernel, -1 if it did not run. */
-#define ESLAM_PROF_KERNELS 12
+#define ESLAM_PROF_KERNELS 13
 int eslam_profile_enable(int on);
 int eslam_profile_read(float* ms_out);
 const char* eslam_profile_name(int kernel_id);

@@ -113,6 +113,7 @@ SIGNATURES = {
     "eslam_render_bwd_loss_h": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _BP, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eslam_decode_fwd": (_i, [_PP, _DP, _BP, _vp, _i64, _i, _vp, _vp, _vp]),
+    "eslam_sdf_grad": (_i, [_PP, _DP, _BP, _vp, _i64, _i, _vp, _vp, _vp]),
     "eslam_sdf_grid": (_i, [_PP, _DP, _BP, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _vp, _vp]),
     "eslam_mc_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "eslam_mc_count": (_i, [_vp, _i64, _i64, _i64, _f, _vp, _vp, _vp]),
@@ -143,6 +144,7 @@ SIGNATURES = {
     "eslam_viewer_mesh": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _i, _i, _vp, _vp]),
     "eslam_viewer_points": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i, _f, _f, _f, _f, _i, _i, _f, _f, _vp, _vp]),
     "eslam_viewer_resolve": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "eslam_shade_vertices": (_i, [_vp, _vp, _vp, _i64, _BP, _f, _vp, _vp]),
     "eslam_depth_l1_workspace_bytes": (_i64, [_i]),
     "eslam_depth_l1": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "eslam_views_see_points": (_i, [_vp, _i64, _vp, _i, _f, _f, _f, _f, _i, _i, _vp, _vp]),
@@ -177,7 +179,7 @@ SIGNATURES = {
     "eslam_keyframe_overlap": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _vp, _vp]),
 }
 
-PROF_KERNELS = 12           # ESLAM_PROF_KERNELS
+PROF_KERNELS = 13          # ESLAM_PROF_KERNELS
 
 
 class AdamTensor(ctypes.Structure):   # eslam_adam_tensor_t

@@ -336,3 +336,66 @@ extern "C" int eslam_viewer_resolve(int n_views, int H, int W, int bg_r, int bg_
                        (const unsigned long long*)workspace, npix, bg, image, depth);
     return eslam_check_launch("viewer_resolve_kernel");
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// headlight Lambert shading of vertex colours, per view, before rasterisation (the light sits at the camera centre)
+// ---------------------------------------------------------------------------------------------------------
+// One vertex per lane, float32 operation by operation: l = c - v; nn = (nx nx + ny ny) + nz nz, ll likewise;
+// k = 1 when nn == 0 or ll == 0, else ambient + (1 - ambient) max(0, ((nx lx + ny ly) + nz lz) / (sqrt(nn) sqrt(ll)));
+// channel = (uint8)floor(min(255, c k) + 0.5), alpha 255.
+__global__ __launch_bounds__(RS_THREADS) void shade_vertices_kernel(const float* __restrict__ verts, const float* __restrict__ normals,
+                                                                    const uint32_t* __restrict__ rgba, int64_t V, float cx, float cy,
+                                                                    float cz, float ambient, uint32_t* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * RS_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x; i < V; i += stride) {
+        const float nx = normals[3 * i], ny = normals[3 * i + 1], nz = normals[3 * i + 2];
+        const float lx = cx - verts[3 * i], ly = cy - verts[3 * i + 1], lz = cz - verts[3 * i + 2];
+        const float nn = nx * nx + ny * ny + nz * nz, ll = lx * lx + ly * ly + lz * lz;
+        float k = 1.0f;
+        if (nn != 0.0f && ll != 0.0f) {
+            const float c = (nx * lx + ny * ly + nz * lz) / (sqrtf(nn) * sqrtf(ll));
+            k = ambient + (1.0f - ambient) * fmaxf(0.0f, c);
+        }
+        const uint32_t col = rgba ? rgba[i] : 0x00c8c8c8u;
+        uint32_t o = 0xff000000u;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float c = (float)((col >> (8 * ch)) & 255u) * k;
+            o |= (uint32_t)floorf(fminf(255.0f, c) + 0.5f) << (8 * ch);
+        }
+        out[i] = o;
+    }
+}
+
+extern "C" int eslam_shade_vertices(const float* verts, const float* normals, const uint8_t* colors, int64_t n_verts,
+                                    const float* cam_center3_host, float ambient, uint8_t* out, eslam_stream_t stream) {
+    if (n_verts < 0 || n_verts > INT32_MAX) {
+        eslam_set_error("eslam_shade_vertices: bad size (%lld vertices)", (long long)n_verts);
+        return 1;
+    }
+    if (!(ambient >= 0.0f && ambient <= 1.0f)) {
+        eslam_set_error("eslam_shade_vertices: ambient %g outside [0, 1]", (double)ambient);
+        return 1;
+    }
+    if (!cam_center3_host) {
+        eslam_set_error("eslam_shade_vertices: null argument");
+        return 1;
+    }
+    if (!isfinite(cam_center3_host[0]) || !isfinite(cam_center3_host[1]) || !isfinite(cam_center3_host[2])) {
+        eslam_set_error("eslam_shade_vertices: the camera centre is not finite");
+        return 1;
+    }
+    if (n_verts == 0) return 0;
+    if (!verts || !normals || !out) {
+        eslam_set_error("eslam_shade_vertices: null argument");
+        return 1;
+    }
+    if (((uintptr_t)out & 3) || ((uintptr_t)colors & 3)) {
+        eslam_set_error("eslam_shade_vertices: colours must be 4-byte aligned");
+        return 1;
+    }
+    hipLaunchKernelGGL(shade_vertices_kernel, dim3(rs_blocks(n_verts, RS_MAX_BLOCKS)), dim3(RS_THREADS), 0, (hipStream_t)stream,
+                       verts, normals, (const uint32_t*)colors, n_verts, cam_center3_host[0], cam_center3_host[1],
+                       cam_center3_host[2], ambient, (uint32_t*)out);
+    return eslam_check_launch("shade_vertices_kernel");
+}

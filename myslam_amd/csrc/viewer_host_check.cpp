@@ -82,6 +82,21 @@ int main() {
     expect(eslam_viewer_resolve(1, 16, 16, 255, 255, 255, nullptr, bytes + 512, nullptr, nullptr) != 0, "resolve, null workspace");
     expect(eslam_viewer_resolve(1, 16, 16, 255, 255, 255, bytes, nullptr, nullptr, nullptr) != 0, "resolve, null image");
     expect(eslam_viewer_resolve(0, 16, 16, 255, 255, 255, nullptr, nullptr, nullptr, nullptr) == 0, "resolve, no views is valid");
+    // vertex shading
+    const float cam[3] = {0.0f, 0.0f, -1.0f}, cam_nan[3] = {0.0f, NAN, 0.0f};
+    expect(eslam_shade_vertices(f, f + 16, bytes, -1, cam, 0.3f, bytes + 512, nullptr) != 0, "shade, negative vertices");
+    expect(eslam_shade_vertices(f, f + 16, bytes, (int64_t)INT32_MAX + 1, cam, 0.3f, bytes + 512, nullptr) != 0, "shade, vertices beyond int32");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, cam, -0.1f, bytes + 512, nullptr) != 0, "shade, ambient below 0");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, cam, 1.5f, bytes + 512, nullptr) != 0, "shade, ambient above 1");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, cam, NAN, bytes + 512, nullptr) != 0, "shade, ambient not a number");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, nullptr, 0.3f, bytes + 512, nullptr) != 0, "shade, null camera centre");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, cam_nan, 0.3f, bytes + 512, nullptr) != 0, "shade, camera centre not finite");
+    expect(eslam_shade_vertices(nullptr, f + 16, bytes, 4, cam, 0.3f, bytes + 512, nullptr) != 0, "shade, null vertices");
+    expect(eslam_shade_vertices(f, nullptr, bytes, 4, cam, 0.3f, bytes + 512, nullptr) != 0, "shade, null normals");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, cam, 0.3f, nullptr, nullptr) != 0, "shade, null output");
+    expect(eslam_shade_vertices(f, f + 16, bytes + 1, 4, cam, 0.3f, bytes + 512, nullptr) != 0, "shade, misaligned colours");
+    expect(eslam_shade_vertices(f, f + 16, bytes, 4, cam, 0.3f, bytes + 513, nullptr) != 0, "shade, misaligned output");
+    expect(eslam_shade_vertices(nullptr, nullptr, nullptr, 0, cam, 0.3f, nullptr, nullptr) == 0, "shade, no vertices is valid");
     if (failures == 0) printf("viewer host check ok\n");
     return failures ? 1 : 0;
 }

@@ -918,6 +918,30 @@ def decode_sdf_only(pts, bound6, all_planes, decoders):
     return out
 
 
+def sdf_gradient(pts, bound6, all_planes, decoders, unit=False):
+    """(sdf [...], grad [...,3]) of pts [...,3] world coordinates: the SDF and its gradient with respect to the point in one
+    launch (eslam_sdf_grad), no autograd.  sdf is decode_sdf_only's bit for bit; grad is what autograd of that sdf gives.
+    unit: rows divided by their length, zero rows kept zero.  Geometry planes + SDF decoder only, float32 (with half copies
+    around, the float32 masters are read)."""
+    _hip.require_gpu_f32("p", pts)
+    if pts.dim() < 1 or pts.shape[-1] != 3:
+        raise RuntimeError(f"p: expected points [...,3], got {tuple(pts.shape)}")
+    shape = pts.shape[:-1]
+    pts = _c(pts.detach().reshape(-1, 3))
+    N = pts.shape[0]
+    dev = pts.device
+    lib = _hip.lib()
+    geo = tuple(all_planes[:3]) + tuple(all_planes[:3])
+    arr, _ = _hip.make_planes(geo)
+    dec, keep = _hip.make_decoders(decoder_params(decoders), beta_tensor(10, dev))
+    sdf = torch.empty(N, device=dev)
+    grad = torch.empty(N, 3, device=dev)
+    with _hip.on_device(dev):
+        _hip.check(lib.eslam_sdf_grad(arr, ctypes.byref(dec), _hip.make_bound(bound6), _hip.ptr(pts), N, 1 if unit else 0,
+                                      _hip.ptr(sdf), _hip.ptr(grad), _hip.stream_handle(dev)), "eslam_sdf_grad")
+    return sdf.reshape(shape), grad.reshape(*shape, 3)
+
+
 class SampleRaysFn(torch.autograd.Function):
     """rays_o, rays_d, depth, color = SampleRaysFn.apply(c2ws, indices, depths, colors, geom)   (common.py:87-153)"""
 
@@ -1806,8 +1830,42 @@ def _u8_rows(name, t, dev, n=None):
     return out
 
 
+def shade_vertices(verts, normals, colors, cam_center, ambient=0.3):
+    """uint8 [V,4] on the GPU: vertex colours under a headlight at cam_center (3 floats, host), for one view
+    (eslam_shade_vertices): c k per channel, k = ambient + (1 - ambient) max(0, n^ . l^), l = cam_center - v, k = 1 where n or l
+    has zero length; alpha 255.  verts, normals float32 [V,3] on the GPU; colors uint8 [V,3|4] on the GPU or None = 200 grey."""
+    v = torch.as_tensor(verts)
+    n = torch.as_tensor(normals)
+    _hip.require_gpu_f32("verts", v)
+    _hip.require_gpu_f32("normals", n)
+    dev = v.device
+    v = _c(v.detach().reshape(-1, 3))
+    n = _c(n.detach().to(dev).reshape(-1, 3))
+    if n.shape[0] != v.shape[0]:
+        raise RuntimeError(f"normals: expected one normal per vertex ({v.shape[0]}), got {n.shape[0]}")
+    c = None
+    if colors is not None:
+        if not torch.as_tensor(colors).is_cuda:
+            raise RuntimeError("colors: expected a tensor on the GPU; the renderer has no CPU fallback")
+        c = _u8_rows("colors", colors, dev, v.shape[0])
+        if c.shape[0] != v.shape[0]:
+            raise RuntimeError(f"colors: expected one colour per vertex ({v.shape[0]}), got {c.shape[0]}")
+    return _shade_prepared(v, n, c, cam_center, ambient, torch.empty(v.shape[0], 4, dtype=torch.uint8, device=dev))
+
+
+def _shade_prepared(v, n, c, cam_center, ambient, out):
+    """shade_vertices on arguments already checked and laid out (v, n float32 [V,3], c uint8 [V,4] or None, out uint8 [V,4],
+    all contiguous on one GPU): the launch alone.  Returns out."""
+    dev = v.device
+    centre = (ctypes.c_float * 3)(*[float(x) for x in cam_center])
+    with _hip.on_device(dev):
+        _hip.check(_hip.lib().eslam_shade_vertices(_hip.ptr(v), _hip.ptr(n), _hip.ptr(c), v.shape[0], centre, float(ambient),
+                                                   _hip.ptr(out), _hip.stream_handle(dev)), "eslam_shade_vertices")
+    return out
+
+
 def render_view(meshes, points, c2ws, K, H, W, background=(255, 255, 255), z_near=_hip.RASTER_Z_NEAR, z_far=_hip.RASTER_Z_FAR,
-                cull_backfaces=True, chunk=8, large_area=0, return_depth=False):
+                cull_backfaces=True, chunk=8, large_area=0, return_depth=False, shade=False, ambient=0.3):
     """uint8 [n,H,W,3] on the GPU: the colour images of meshes and point clouds from the cameras c2ws [n,4,4] (the
     convention of render_mesh_depth: the camera looks along +z, y down), K = (fx, fy, cx, cy); what the reference's open3d
     window shows (visualizer_util.py:178-200): meshes unlit with their vertex colours, back faces hidden when
@@ -1815,9 +1873,12 @@ def render_view(meshes, points, c2ws, K, H, W, background=(255, 255, 255), z_nea
     meshes: a list of (verts float32 [V,3], faces [F,3], colors uint8 [V,3|4] or None = grey); points: a list of
     (xyz float32 [N,3], rgb uint8 [3|4] for all or [N,3|4], size in pixels).  All tensors on one GPU.  Views are rendered `chunk` at a
     time; the poses are inverted on the host in float64.  With return_depth also float32 [n,H,W]: the camera-space z of the
-    winning fragment, 0 where the background shows.  The images depend neither on the order of the lists nor on large_area."""
+    winning fragment, 0 where the background shows.  The images depend neither on the order of the lists nor on large_area.
+    A mesh may carry a fourth element, normals float32 [V,3] on the GPU.  With shade=True the meshes that have normals are lit
+    by a headlight at each view's camera centre (shade_vertices with `ambient`, then rasterised with those colours), one view
+    at a time; meshes without normals, and every call with shade=False, are drawn unlit as before."""
     ms, ps, dev = [], [], None
-    for k, (verts, faces, colors) in enumerate(meshes):
+    for k, (verts, faces, colors, *rest) in enumerate(meshes):
         v = torch.as_tensor(verts)
         _hip.require_gpu_f32(f"meshes[{k}] verts", v)
         dev = v.device if dev is None else dev
@@ -1833,7 +1894,16 @@ def render_view(meshes, points, c2ws, K, H, W, background=(255, 255, 255), z_nea
             c = _u8_rows(f"meshes[{k}] colors", colors, dev, v.shape[0])
             if c.shape[0] != v.shape[0]:
                 raise RuntimeError(f"meshes[{k}] colors: expected one colour per vertex ({v.shape[0]}), got {c.shape[0]}")
-        ms.append((v, f, c))
+        nrm = None
+        if shade and rest and rest[0] is not None:
+            nrm = torch.as_tensor(rest[0])
+            _hip.require_gpu_f32(f"meshes[{k}] normals", nrm)
+            nrm = _c(nrm.detach().reshape(-1, 3))
+            if nrm.shape[0] != v.shape[0]:
+                raise RuntimeError(f"meshes[{k}] normals: expected one normal per vertex ({v.shape[0]}), got {nrm.shape[0]}")
+        # (a lit mesh's colours are prepared once; its shaded colours live in one buffer that every view overwrites in turn,
+        # in stream order behind the previous view's rasterisation)
+        ms.append((v, f, c, nrm, torch.empty(v.shape[0], 4, dtype=torch.uint8, device=dev) if nrm is not None else None))
     for k, (xyz, rgb, size) in enumerate(points):
         p = torch.as_tensor(xyz)
         _hip.require_gpu_f32(f"points[{k}] xyz", p)
@@ -1844,6 +1914,10 @@ def render_view(meshes, points, c2ws, K, H, W, background=(255, 255, 255), z_nea
         dev = torch.device("cuda", torch.cuda.current_device())
     fx, fy, cx, cy = (float(k) for k in K)
     H, W, chunk = int(H), int(W), max(1, int(chunk))
+    lit = any(m[3] is not None for m in ms)
+    if lit:             # the light moves with the camera: colours per view
+        chunk = 1
+        centres = torch.as_tensor(c2ws).detach().to("cpu", torch.float32).reshape(-1, 4, 4)[:, :3, 3].tolist()
     bg = [int(b) for b in background]
     w2c = _w2c_rows(c2ws, dev)
     n = w2c.shape[0]
@@ -1861,7 +1935,9 @@ def render_view(meshes, points, c2ws, K, H, W, background=(255, 255, 255), z_nea
             k = min(chunk, n - lo)
             cam = (_hip.ptr(w2c[lo:]), k, fx, fy, cx, cy, H, W, float(z_near), float(z_far))
             _hip.check(lib.eslam_viewer_begin(k, H, W, _hip.ptr(ws), st), "eslam_viewer_begin")
-            for v, f, c in ms:
+            for v, f, c, nrm, lit_c in ms:
+                if nrm is not None:
+                    c = _shade_prepared(v, nrm, c, centres[lo], ambient, lit_c)
                 _hip.check(lib.eslam_viewer_mesh(_hip.ptr(v), v.shape[0], _hip.ptr(f), f.shape[0], _hip.ptr(c) if c is not None else None,
                                                  *cam, int(bool(cull_backfaces)), int(large_area), _hip.ptr(ws), st), "eslam_viewer_mesh")
             for p, c, size in ps:

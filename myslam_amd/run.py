@@ -42,12 +42,16 @@ def main(argv=None):
                         help='render every N-th frame at its estimated pose after the run; PSNR, SSIM, depth L1 to render_eval.json')
     parser.add_argument('--clean_mesh', type=int, metavar='N',
                         help='also write every culled mesh without its connected components of fewer than N faces')
+    parser.add_argument('--mesh_normals', action='store_true',
+                        help='write unit vertex normals (+grad sdf of the learned field) into every mesh file')
     args = parser.parse_args(argv)
     cfg = config.load_config(args.config, default_config_for(args.config))
     if args.render_eval is not None:
         cfg['render_eval'] = dict(every=args.render_eval)
     if args.clean_mesh is not None:
         cfg['meshing']['clean_min_faces'] = args.clean_mesh
+    if args.mesh_normals:
+        cfg['meshing']['normals'] = True
     eslam = ESLAM(cfg, args)
     eslam.run()
     return eslam

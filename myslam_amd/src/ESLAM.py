@@ -25,6 +25,8 @@ Written under <output>/:
                                the visualisers' panels: frame NNNNN, iteration IIII, every vis_freq frames and
                                vis_inside_freq iterations; frame 0 skipped with no_vis_on_first_frame (Tracker.py:276-302,
                                Mapper.py:308-310)
+    (with meshing.normals: true - ours; absent or false = off - every mesh file above carries unit vertex normals nx, ny, nz:
+    +grad sdf of the learned field at the file's own vertices, Mesher.vertex_normals; vertices, faces and colours unchanged)
     render_eval.json           with the top-level key render_eval: {every: N} (ours, like mixed_precision; absent or 0 = off):
                                PSNR, SSIM and depth L1 of every N-th frame rendered at its estimated pose, and their means
 """
@@ -36,11 +38,11 @@ import torch
 from .. import checkpoint, eval_ate
 from ..scene import scene_from_config
 from ..slam import Slam, SlamConfig
-from .tools.clean_mesh import clean_mesh
+from .tools.clean_mesh import clean_mesh, clean_path
 from .tools.cull_mesh import cull_mesh, culled_path
 from .utils.datasets import FrameStream, get_dataset
 from .utils.Frame_Visualizer import Frame_Visualizer
-from .utils.Mesher import Mesher
+from .utils.Mesher import Mesher, read_ply, write_ply
 
 
 class ESLAM:
@@ -76,6 +78,7 @@ class ESLAM:
         self.no_mesh_on_first_frame = bool(m.get('no_mesh_on_first_frame', False))
         self.eval_rec = bool(cfg['meshing']['eval_rec'])
         self.clean_min_faces = int(cfg['meshing'].get('clean_min_faces', 0) or 0)
+        self.mesh_normals = bool(cfg['meshing'].get('normals', False))
         self.render_eval_every = int((cfg.get('render_eval') or {}).get('every', 0) or 0)
         self.render_eval = None
         self.visualizers = {}
@@ -100,12 +103,23 @@ class ESLAM:
     def _mesh(self, s, mesh_out_file, n_poses):
         """Mapper.py:444-446 / :454-455: the mesh, then its copy culled to what the frames see from the estimated poses."""
         with s._precision():
-            self.mesher.get_mesh(mesh_out_file, s.all_planes, s.decoders, s.keyframe_dict, self.device)
+            self.mesher.get_mesh(mesh_out_file, s.all_planes, s.decoders, s.keyframe_dict, self.device,
+                                 normals=self.mesh_normals)
         if os.path.exists(mesh_out_file):                                # (no surface: get_mesh says so and writes nothing)
             est = torch.stack([c.detach().cpu() for c in s.estimate_c2w_list[:n_poses]], 0)
             cull_mesh(mesh_out_file, self.cfg, self.args, self.device, estimate_c2w_list=est)
+            self._add_normals(s, culled_path(mesh_out_file))
             if self.clean_min_faces > 0:
                 clean_mesh(culled_path(mesh_out_file), device=self.device, min_faces=self.clean_min_faces)
+                self._add_normals(s, clean_path(culled_path(mesh_out_file)))
+
+    def _add_normals(self, s, path):
+        """meshing.normals: the file rewritten with the field's normals at its own vertices (culling and clean-up move no
+        vertex, so nothing is threaded through them: one launch per file)."""
+        if not self.mesh_normals or not os.path.exists(path):
+            return
+        v, f, c = read_ply(path)
+        write_ply(path, v, f, c, self.mesher.vertex_normals(v, s.all_planes, s.decoders))
 
     def _on_frame(self, s, idx):
         """Mapper.py:437-446 for a frame the mapper has seen (its loop runs at mapped frames and at the last one)."""

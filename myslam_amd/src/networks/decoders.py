@@ -63,6 +63,18 @@ class Decoders(nn.Module):
         """decoders.py:107-125."""
         return self._decode(p_nor.reshape(-1, 3), _UNIT_BOUND, all_planes)[:, :3]
 
+    def sdf_gradient(self, p, all_planes, unit=False):
+        """p [...,3] world coordinates -> (sdf [...], d sdf / d p [...,3]) in one fused launch, no autograd
+        (ops.sdf_gradient on self.bound; the reference has no equivalent).  Float32 planes and decoders."""
+        with torch.no_grad():
+            planes = ops.planes_for_kernels(all_planes, p.numel() // 3)
+            return ops.sdf_gradient(p, ops.bound_to_host(self.bound), planes, self, unit=unit)
+
+    def sdf_normals(self, p, all_planes):
+        """p [...,3] world coordinates -> unit surface normals [...,3] = the direction of +grad sdf (towards free space);
+        zeros where the gradient vanishes."""
+        return self.sdf_gradient(p, all_planes, unit=True)[1]
+
     def forward(self, p, all_planes):
         """decoders.py:127-146: p [...,3] world coordinates -> raw [...,4] = (rgb, sdf)."""
         p_shape = p.shape

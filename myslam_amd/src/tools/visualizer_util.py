@@ -23,7 +23,7 @@ import torch
 
 from ... import _hip
 from ... import ops
-from ..utils.Mesher import read_ply
+from ..utils.Mesher import read_ply, read_ply_with_normals
 
 WINDOW_H, WINDOW_W = 1080, 1920
 FOV_Y_DEG = 60.0
@@ -67,8 +67,10 @@ def window_intrinsics(H, W):
 
 class SLAMFrontend:
     def __init__(self, output, init_pose, cam_scale=1, save_rendering=False, near=0, estimate_c2w_list=None,
-                 gt_c2w_list=None, size=(WINDOW_H, WINDOW_W), device=None):
-        """size: the image's (H, W); the reference's window everywhere but in tests."""
+                 gt_c2w_list=None, size=(WINDOW_H, WINDOW_W), device=None, shaded=False, ambient=0.3):
+        """size: the image's (H, W); the reference's window everywhere but in tests.  shaded (ours): meshes whose PLY carries
+        vertex normals are lit by a headlight (ops.render_view(shade=True, ambient=ambient)); the reference's window is unlit."""
+        self.shaded, self.ambient = bool(shaded), float(ambient)
         self.output = output
         self.cam_scale = cam_scale
         self.save_rendering = save_rendering
@@ -97,9 +99,11 @@ class SLAMFrontend:
         self.cameras[index + GT_KEY if gt else index] = (self._gpu(pts), pose)
 
     def update_mesh(self, path):
-        v, f, c = read_ply(path)
+        v, f, c, nrm = read_ply_with_normals(path) if self.shaded else read_ply(path) + (None,)
         col = None if c is None else self._gpu(np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5), torch.uint8)
-        self.mesh = (self._gpu(v), self._gpu(f, torch.int32), col)
+        if self.shaded and nrm is None:
+            print(f'WARNING: {path} has no vertex normals (run with meshing.normals); drawn unlit')
+        self.mesh = (self._gpu(v), self._gpu(f, torch.int32), col, None if nrm is None else self._gpu(nrm))
 
     def update_cam_trajectory(self, c2w_list, gt):
         i = c2w_list
@@ -126,7 +130,8 @@ class SLAMFrontend:
         points += [(pts, GREEN if gt else RED, POINT_SIZE) for gt, pts in sorted(self.traj.items()) if pts is not None]
         points = [(p, torch.tensor(c, dtype=torch.uint8), s) for p, c, s in points]
         return ops.render_view(meshes, points, self.view[None], self.K, self.H, self.W, background=BACKGROUND,
-                               z_near=self.z_near, z_far=Z_FAR, cull_backfaces=True, chunk=1)[0]
+                               z_near=self.z_near, z_far=Z_FAR, cull_backfaces=True, chunk=1, shade=self.shaded,
+                               ambient=self.ambient)[0]
 
     def capture(self, index):
         """Writes render() to <output>/tmp_rendering/{index:06d}.jpg (visualizer_util.py:171-176); returns the path."""

@@ -180,9 +180,19 @@ def grid_axes(marching_cubes_bound, resolution):
 NO_SURFACE = 'marching_cubes error. Possibly no surface extracted from the level set.'
 
 
-def extract_mesh(self, all_planes, decoders, keyframe_dict, device='cuda:0', color=True):
+def vertex_normals(self, vertices, all_planes, decoders):
+    """float32 numpy [V,3]: the unit surface normals of a mesh at its own vertices (scene units, as extract_mesh and the
+    files give them): +grad sdf of the field at vertices * self.scale, one fused launch (Decoders.sdf_normals).  The
+    direction is towards free space, the side marching cubes' face winding faces.  Zero where the gradient vanishes."""
+    dev = ops.decoder_params(decoders)[0].device
+    v = torch.as_tensor(np.ascontiguousarray(vertices, dtype=np.float32)).reshape(-1, 3).to(dev)
+    return decoders.sdf_normals(v * self.scale, all_planes).cpu().numpy()
+
+
+def extract_mesh(self, all_planes, decoders, keyframe_dict, device='cuda:0', color=True, normals=False):
     """get_mesh without the file: (vertices float32 [V,3] in scene units / self.scale, faces int32 [F,3],
-    colours float32 [V,3] or None) as numpy arrays, or None when the level set has no surface."""
+    colours float32 [V,3] or None) as numpy arrays, or None when the level set has no surface.  normals=True: a fourth
+    element, the unit normals float32 [V,3] of vertex_normals."""
     with torch.no_grad():
         dev = torch.device(device)
         x, y, z = grid_axes(self.marching_cubes_bound, self.resolution)
@@ -200,13 +210,15 @@ def extract_mesh(self, all_planes, decoders, keyframe_dict, device='cuda:0', col
             colours = eval_points(self, verts, all_planes, decoders)[:, :3].cpu().numpy()
         vertices = verts.cpu().numpy()
         vertices /= self.scale
+        if normals:
+            return vertices, faces.cpu().numpy(), colours, vertex_normals(self, vertices, all_planes, decoders)
         return vertices, faces.cpu().numpy(), colours
 
 
-def get_mesh(self, mesh_out_file, all_planes, decoders, keyframe_dict, device='cuda:0', color=True):
+def get_mesh(self, mesh_out_file, all_planes, decoders, keyframe_dict, device='cuda:0', color=True, normals=False):
     """Mesher.py:188-262: extract the mesh and write it as a binary PLY (write_ply).  No surface: the reference's message,
-    no file."""
-    m = extract_mesh(self, all_planes, decoders, keyframe_dict, device, color)
+    no file.  normals=True: the file carries the vertex normals of vertex_normals (nx, ny, nz)."""
+    m = extract_mesh(self, all_planes, decoders, keyframe_dict, device, color, normals)
     if m is None:
         print(NO_SURFACE)
         return
@@ -236,24 +248,34 @@ class Mesher:
     keyframe_points = keyframe_points
     get_bound_from_frames = get_bound_from_frames
     get_bound_from_frames_tsdf = get_bound_from_frames_tsdf
+    vertex_normals = vertex_normals
     extract_mesh = extract_mesh
     get_mesh = get_mesh
 
 
-def write_ply(path, vertices, faces, colors=None):
-    """Binary little-endian PLY: vertex x y z float (+ red green blue alpha uchar, colour round(255 c) clipped, alpha
-    255), face `list uchar int vertex_indices`."""
+def write_ply(path, vertices, faces, colors=None, normals=None):
+    """Binary little-endian PLY: vertex x y z float (+ nx ny nz float directly after z, the order open3d, MeshLab and
+    trimesh write) (+ red green blue alpha uchar, colour round(255 c) clipped, alpha 255), face
+    `list uchar int vertex_indices`."""
     v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
     f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
             "property float x", "property float y", "property float z"]
     vfields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if nrm.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply: {nrm.shape[0]} normals for {v.shape[0]} vertices")
+        head += ["property float nx", "property float ny", "property float nz"]
+        vfields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue", "property uchar alpha"]
         vfields += [("red", "u1"), ("green", "u1"), ("blue", "u1"), ("alpha", "u1")]
     head += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     vrec = np.empty(v.shape[0], dtype=vfields)
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         c = np.clip(np.round(255.0 * np.asarray(colors, dtype=np.float64)), 0, 255).astype(np.uint8).reshape(-1, 3)
         vrec["red"], vrec["green"], vrec["blue"] = c[:, 0], c[:, 1], c[:, 2]
@@ -362,11 +384,8 @@ def _fan(polys):
     return np.array(tris, dtype=np.int64).reshape(-1, 3)
 
 
-def read_ply(path):
-    """(vertices float32 [V,3], faces int64 [F,3], colours float32 [V,3] in [0, 1] or None) of a PLY file: ASCII or
-    binary (either byte order), any scalar vertex properties (x, y, z and red, green, blue are used; normals and other
-    properties are skipped), faces as a `vertex_indices` (or `vertex_index`) list of any count and index type, polygons
-    fan-triangulated from their first vertex, other elements skipped.  Reads what write_ply writes, bit for bit."""
+def _ply_elements(path):
+    """[(element name, {scalar property: array}, {list property: arrays})] of a PLY file, in file order."""
     with open(path, "rb") as fh:
         data = fh.read()
     fmt, elements, off = _ply_header(data)
@@ -374,20 +393,49 @@ def read_ply(path):
     if fmt == "ascii":
         lines = [ln for ln in data[off:].decode("ascii").splitlines() if ln.strip()]
     bo = ">" if fmt == "binary_big_endian" else "<"
-    verts, faces, colors = None, np.zeros((0, 3), dtype=np.int64), None
+    out = []
     for name, n, props in elements:
         if fmt == "ascii":
             scal, lists, pos = _ply_read_ascii(lines, pos, n, props)
         else:
             scal, lists, off = _ply_read_binary(data, off, n, props, bo)
+        out.append((name, scal, lists))
+    return out
+
+
+def _mesh_of(elements, path):
+    verts, faces, colors, normals = None, np.zeros((0, 3), dtype=np.int64), None, None
+    for name, scal, lists in elements:
         if name == "vertex":
             verts = np.stack([scal["x"], scal["y"], scal["z"]], 1).astype(np.float32)
             if all(c in scal for c in ("red", "green", "blue")):
                 c = np.stack([scal["red"], scal["green"], scal["blue"]], 1)
                 colors = (c.astype(np.float32) / 255.0).astype(np.float32) if c.dtype.kind in "iu" else c.astype(np.float32)
+            if all(c in scal for c in ("nx", "ny", "nz")):
+                normals = np.stack([scal["nx"], scal["ny"], scal["nz"]], 1).astype(np.float32)
         elif name == "face":
             key = "vertex_indices" if "vertex_indices" in lists else "vertex_index"
             faces = _fan(lists[key]).astype(np.int64)
     if verts is None:
         raise ValueError(f"{path}: no vertex element")
-    return verts, faces, colors
+    return verts, faces, colors, normals
+
+
+def read_ply(path):
+    """(vertices float32 [V,3], faces int64 [F,3], colours float32 [V,3] in [0, 1] or None) of a PLY file: ASCII or
+    binary (either byte order), any scalar vertex properties (x, y, z and red, green, blue are used; normals and other
+    properties are skipped), faces as a `vertex_indices` (or `vertex_index`) list of any count and index type, polygons
+    fan-triangulated from their first vertex, other elements skipped.  Reads what write_ply writes, bit for bit."""
+    return _mesh_of(_ply_elements(path), path)[:3]
+
+
+def read_ply_with_normals(path):
+    """read_ply's three arrays and the vertex normals (nx, ny, nz) float32 [V,3], or None when the vertices carry none, from
+    one pass over the file."""
+    return _mesh_of(_ply_elements(path), path)
+
+
+def read_ply_normals(path):
+    """float32 [V,3]: the vertex normals (nx, ny, nz) of a PLY file, or None when its vertices carry none.  Reads what
+    write_ply(normals=...) writes, bit for bit."""
+    return _mesh_of(_ply_elements(path), path)[3]

@@ -1,7 +1,7 @@
 """The offline viewer, as the reference's visualizer.py drives it, without a window:
 
     python -m myslam_amd.visualizer configs/Replica/room0.yaml [--output D] [--save_rendering] [--top_view] [--no_gt_traj]
-                                    [--every K] [--size H W]
+                                    [--every K] [--size H W] [--shaded [--ambient A]]
 
 Replays a finished run from its output folder: the newest checkpoint's estimated and ground-truth trajectories
 (translations divided by the config's `scale`), and for every frame i the mesh mesh/{i:05d}_mesh_culled.ply when the
@@ -10,7 +10,9 @@ the GPU (src/tools/visualizer_util.py, ops.render_view).  With --save_rendering 
 default 1) is written to <output>/tmp_rendering/{i:06d}.jpg; without it only the final state is written, to
 <output>/vis.jpg (the reference shows a window instead).  The images are deterministic: the reference captures whatever
 its GL loop showed between sleeps.  --size (ours) is the image's height and width, the reference's 1080 x 1920 window
-by default.  No video is encoded: the reference's ffmpeg command line is printed for the user to run.
+by default.  --shaded (ours): meshes whose PLY carries vertex normals (a run with meshing.normals) are lit by a headlight at
+the viewing camera, k = ambient + (1 - ambient) max(0, n . l) with --ambient A (default 0.3); a mesh without normals is drawn
+unlit with one warning line.  No video is encoded: the reference's ffmpeg command line is printed for the user to run.
 
 --top_view: the reference asks trimesh for the newest mesh's minimum-volume oriented box (oriented_bounds, ordered=False)
 and views along that box's z axis, whichever axis that search ended on.  Here the box is the one of
@@ -51,7 +53,11 @@ def main(argv=None):
     parser.add_argument('--no_gt_traj', action='store_true', help='not visualize gt trajectory')
     parser.add_argument('--every', type=int, default=1, metavar='K', help='render every K-th sequence index')
     parser.add_argument('--size', type=int, nargs=2, default=(WINDOW_H, WINDOW_W), metavar=('H', 'W'), help='image size')
+    parser.add_argument('--shaded', action='store_true', help='light meshes that carry vertex normals (headlight Lambert)')
+    parser.add_argument('--ambient', type=float, default=0.3, metavar='A', help='ambient share of the shading, in [0, 1]')
     args = parser.parse_args(argv)
+    if not 0.0 <= args.ambient <= 1.0:
+        parser.error('--ambient must lie in [0, 1]')
     if args.every < 1:
         parser.error('--every must be at least 1')
     cfg = config.load_config(args.config, default_config_for(args.config))
@@ -77,7 +83,8 @@ def main(argv=None):
         raise FileNotFoundError(f'no mesh under {output}/mesh')
     init_pose = top_view_pose(meshfiles[-1]) if args.top_view else gt_c2w_list[0].copy()
     frontend = SLAMFrontend(output, init_pose=init_pose, cam_scale=0.2, save_rendering=args.save_rendering, near=0,
-                            estimate_c2w_list=estimate_c2w_list, gt_c2w_list=gt_c2w_list, size=tuple(args.size))
+                            estimate_c2w_list=estimate_c2w_list, gt_c2w_list=gt_c2w_list, size=tuple(args.size),
+                            shaded=args.shaded, ambient=args.ambient)
     frontend.start()
     written = []
     for i in range(0, N + 1):

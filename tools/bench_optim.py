@@ -14,7 +14,7 @@ def timed(fn, n=50, warm=10):
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / n * 1e3
 
 def kernel_ms(fn, slot=10, n=20):
-    buf = (ctypes.c_float * 12)(); ts = []
+    buf = (ctypes.c_float * _hip.PROF_KERNELS)(); ts = []
     for _ in range(n):
         lib.eslam_profile_enable(1); fn(); torch.cuda.synchronize(); lib.eslam_profile_read(buf); ts.append(buf[slot])
     lib.eslam_profile_enable(0)

@@ -22,7 +22,7 @@ if lowp:
         with ops.mixed_precision(half):
             return wl.step()
 lib = _hip.lib()
-buf = (ctypes.c_float * 12)()
+buf = (ctypes.c_float * _hip.PROF_KERNELS)()
 cal = torch.ones(64 * 1024 * 1024, device=dev)            # 256 MiB: larger than the L2s, read exactly once by the reduction
 for _ in range(3): step()
 torch.cuda.synchronize()

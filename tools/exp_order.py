@@ -35,7 +35,7 @@ def as_orders(p):          # the buffer eslam_ray_order fills: three orders + 4 
     return torch.cat([p, p, p, torch.zeros(4, dtype=torch.int32, device=dev)])
 
 def measure(label):
-    buf = (ctypes.c_float * 12)()
+    buf = (ctypes.c_float * _hip.PROF_KERNELS)()
     for _ in range(5): wl.step()
     acc = {}
     for _ in range(15):
