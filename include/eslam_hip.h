@@ -472,6 +472,72 @@ int64_t eslam_icp_moments_workspace_bytes(void);
 int eslam_icp_moments(const float* src, const float* tgt, const float* dist, const int32_t* idx, int64_t n,
                       float threshold, void* workspace, double* out, eslam_stream_t stream);
 
+/* Exact point-to-mesh distance on a uniform grid of cubic cells (no counterpart in the reference, whose 3D metrics
+ * measure to a sample cloud).  verts [n_verts,3] float32, faces [n_faces,3] int32, queries [n_query,3] float32, device.
+ * Grid rule (eslam_tri_grid_plan, host only; bbox6 = lo/hi per axis of the finite vertices, face_extent = the mean
+ * over the faces of the largest axis extent of the face's box, as the caller measured it):
+ *   E = the largest extent of the box; E = 0 or n_faces = 0: one cell of edge 1.  Otherwise the m axes with extent
+ *   > 1e-6 E span the volume P; the edge is h = max(ESLAM_TRI_CELL_PER_EXTENT * face_extent, (P / MAX_CELLS)^(1/m)),
+ *   with (P / n_faces)^(1/m) in place of the first term when face_extent is not positive and finite;
+ *   dims[d] = max(1, ceil(extent[d] / h)); while their product > MAX_CELLS, h grows by 10 %.  The stored edge is the
+ *   float32 just above h.  A cell of two face extents holds a face in about two cells.
+ * Entries: a face is entered in every cell its axis-aligned box overlaps; a face with a non-finite coordinate or an
+ *   index outside [0, n_verts) is entered nowhere and is never returned.  eslam_tri_count writes total [2] (device,
+ *   int64) = the number of (face, cell) entries and of faces entered; the caller copies total[0] into grid->entries.
+ *   eslam_tri_workspace_bytes and eslam_tri_build fail, before any launch and naming the count, when grid->entries
+ *   is negative or above ESLAM_TRI_MAX_ENTRIES (2^31 - 1).  The workspace keeps, in cell order, three float4 per entry:
+ *   (a, face index bits), (b, 0), (c, 0).
+ * Query: one query per lane, rings of growing Chebyshev radius round the query's clamped cell; it stops when the face
+ *   distance of the searched box, less a slack of 4e-6 (|q|_inf + |box|_inf), squared, reaches the best so far.
+ *   The result is the minimum over ALL entered faces of the per-pair function below, (d2, face) lexicographically:
+ *   equal d2 go to the smaller face index.  dist [n_query] = sqrtf(d2), face [n_query], closest [n_query,3] (may be
+ *   NULL).  max_dist as for eslam_nn_query: only dist < max_dist counts.  A query with a non-finite coordinate, or
+ *   with no face in reach, gets dist = inf, face = -1, closest = NaN.  n_query = 0 or grid->entries = 0 returns 0
+ *   without a launch and writes nothing: with no entries the caller fills (inf, -1).
+ *   flags: ESLAM_TRI_INPUT_ORDER = queries in input order (no query workspace); by default in cell order.
+ * The per-pair function (Ericson's closest point on a triangle), float32 operation by operation, no contraction;
+ * dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z;  ab = b - a,  ac = c - a  (a vertex region returns the vertex itself):
+ *   ap = q - a;  d1 = dot(ab, ap);  d2 = dot(ac, ap);          d1 <= 0 and d2 <= 0                 -> a
+ *   bp = ap - ab;  d3 = dot(ab, bp);  d4 = dot(ac, bp);        d3 >= 0 and d4 <= d3                -> b     
+ *   vc = d1 d4 - d3 d2;   vc <= 0, d1 >= 0, d3 <= 0:           s = d1 - d3,  v = d1 / s            -> a + ab v
+ *   cp = ap - ac;  d5 = dot(ab, cp);  d6 = dot(ac, cp);        d6 >= 0 and d5 <= d6                -> c     
+ *   vb = d5 d2 - d1 d6;   vb <= 0, d2 >= 0, d6 <= 0:           s = d2 - d6,  w = d2 / s            -> a + ac w
+ *   va = d3 d6 - d5 d4;   va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: s = (d4 - d3) + (d5 - d6), w = (d4 - d3) / s
+ *                                                                                       -> b + (c - b) w
+ *   otherwise s = (va + vb) + vc,  r = 1 / s,  v = vb r,  w = vc r                      -> (a + ab v) + ac w
+ *   (the tests in this order, the first that holds decides; u t = per component product, then the sum).
+ *   The interior branch also requires va, vb and vc each above tol = (1e-6 (n1(ab) n1(ac))) (m m), with
+ *   n1(u) = (|u.x| + |u.y|) + |u.z| and m = (n1(ap) + n1(ab)) + n1(ac): a bound on the rounding noise of these
+ *   differences of products, below which (collinear and sliver faces) the weights v, w would be arbitrary.
+ *   When the deciding branch has an s that is not positive and finite, or the interior is not clear of tol (zero-area
+ *   and sliver faces, projections within about 1e-4 of a face's size of an edge, overflow), the
+ *   closest point is the nearest of the three segments (a, ab), (a, ac), (b, c - b), the first of equal ones:
+ *   on (o, e): ee = dot(e, e), t = min(max(dot(q - o, e) / ee, 0), 1) when ee is positive and finite, else 0 (a NaN
+ *   quotient gives 0); point o + e t.
+ *   Then d = q - closest, d2 = (d.x d.x + d.y d.y) + d.z d.z.  A pair whose d2 is NaN (overflow: coordinates beyond
+ *   about 1e8) is never selected, so no output is ever NaN.                                                         */
+#define ESLAM_TRI_MAX_CELLS (1 << 24)
+#define ESLAM_TRI_CELL_PER_EXTENT 2
+#define ESLAM_TRI_MAX_ENTRIES 2147483647LL
+#define ESLAM_TRI_INPUT_ORDER 1
+typedef struct {
+    float lo[3];       /* the vertices' minimum corner                              */
+    float cell;        /* edge of the cubic cells                                   */
+    int32_t dims[3];   /* cells per axis                                            */
+    int32_t reserved;
+    int64_t entries;   /* (face, cell) entries: 0 from the plan, then eslam_tri_count's */
+} eslam_tri_grid_t;
+int eslam_tri_grid_plan(int64_t n_faces, const float* bbox6_host, float face_extent, eslam_tri_grid_t* grid);
+int eslam_tri_count(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                    const eslam_tri_grid_t* grid, int64_t* total, eslam_stream_t stream);
+int64_t eslam_tri_workspace_bytes(const eslam_tri_grid_t* grid);
+int eslam_tri_build(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces,
+                    const eslam_tri_grid_t* grid, void* workspace, eslam_stream_t stream);
+int64_t eslam_tri_query_workspace_bytes(const eslam_tri_grid_t* grid, int64_t n_query);
+int eslam_tri_query(const eslam_tri_grid_t* grid, const void* workspace, const float* queries, int64_t n_query,
+                    float max_dist, int flags, void* query_workspace, float* dist, int32_t* face, float* closest,
+                    eslam_stream_t stream);
+
 /* Mesh clean-up (src/tools/clean_mesh.py): the vertex merge of trimesh's process() that closes the reference's
  * src/tools/cull_mesh.py:109, and the connected components behind NICE-SLAM's remove_small_geometry.  verts [n_verts,3]
  * float32, faces [n_faces,3] int32 with every index in [0, n_verts) (the caller checks: the kernels do not).  Counts are

@@ -44,6 +44,15 @@ class NnGrid(ctypes.Structure):       # eslam_nn_grid_t
                 ("reserved", ctypes.c_int32)]
 
 
+class TriGrid(ctypes.Structure):      # eslam_tri_grid_t
+    _fields_ = [("lo", ctypes.c_float * 3), ("cell", ctypes.c_float), ("dims", ctypes.c_int32 * 3),
+                ("reserved", ctypes.c_int32), ("entries", ctypes.c_int64)]
+
+
+TRI_MAX_CELLS = 1 << 24      # ESLAM_TRI_MAX_CELLS
+TRI_CELL_PER_EXTENT = 2      # ESLAM_TRI_CELL_PER_EXTENT
+TRI_MAX_ENTRIES = 2 ** 31 - 1    # ESLAM_TRI_MAX_ENTRIES
+TRI_INPUT_ORDER = 1          # ESLAM_TRI_INPUT_ORDER
 NN_MAX_CELLS = 1 << 24       # ESLAM_NN_MAX_CELLS
 NN_CELLS_PER_POINT = 2       # ESLAM_NN_CELLS_PER_POINT
 NN_INPUT_ORDER = 1           # ESLAM_NN_INPUT_ORDER
@@ -62,6 +71,7 @@ _PP = ctypes.POINTER(PlaneDesc)
 _DP = ctypes.POINTER(DecodersDesc)
 _BP = ctypes.POINTER(ctypes.c_float)
 _GP = ctypes.POINTER(NnGrid)
+_TP = ctypes.POINTER(TriGrid)
 
 # name -> (restype, argtypes); must list every symbol declared in include/eslam_hip.h
 SIGNATURES = {
@@ -131,6 +141,12 @@ SIGNATURES = {
     "eslam_nn_build": (_i, [_vp, _i64, _GP, _vp, _vp]),
     "eslam_nn_query_workspace_bytes": (_i64, [_GP, _i64]),
     "eslam_nn_query": (_i, [_GP, _vp, _i64, _vp, _i64, _f, _i, _vp, _vp, _vp, _vp]),
+    "eslam_tri_grid_plan": (_i, [_i64, _BP, _f, _TP]),
+    "eslam_tri_count": (_i, [_vp, _i64, _vp, _i64, _TP, _vp, _vp]),
+    "eslam_tri_workspace_bytes": (_i64, [_TP]),
+    "eslam_tri_build": (_i, [_vp, _i64, _vp, _i64, _TP, _vp, _vp]),
+    "eslam_tri_query_workspace_bytes": (_i64, [_TP, _i64]),
+    "eslam_tri_query": (_i, [_TP, _vp, _vp, _i64, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "eslam_icp_moments_workspace_bytes": (_i64, []),
     "eslam_icp_moments": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "eslam_mesh_weld_workspace_bytes": (_i64, [_i64]),

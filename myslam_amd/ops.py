@@ -1742,6 +1742,93 @@ def component_face_counts(faces, labels):
     return count
 
 
+class MeshDistance:
+    """Exact distance from points to the triangle mesh (verts float32 [V,3], faces integer [F,3], both on the GPU): a
+    uniform grid built once (eslam_tri_grid_plan / eslam_tri_count / eslam_tri_build), queried any number of times.  One
+    host sync for the bounding box of the finite vertices and the mean face extent the plan takes, one for the entry
+    count; a face index outside [0, V) raises ValueError.  A face with a non-finite coordinate is never returned.  No CPU
+    fallback."""
+
+    def __init__(self, verts, faces):
+        self.verts = _mesh_gpu("verts", verts, torch.float32, 3)
+        self.device = self.verts.device
+        n_verts = self.verts.shape[0]
+        self.faces = _mesh_faces(faces, n_verts)
+        if self.faces.device != self.device:
+            raise RuntimeError(f"MeshDistance: verts on {self.device}, faces on {self.faces.device}")
+        n_faces = self.faces.shape[0]
+        self.grid = _hip.TriGrid()
+        self.faces_entered = 0
+        self.ws = None
+        lib = _hip.lib()
+        stats = None
+        if n_faces:
+            tri = self.verts[self.faces.long()]                                  # [F,3,3]
+            ok = torch.isfinite(tri).all(dim=2).all(dim=1)
+            fin = torch.isfinite(self.verts).all(dim=1)
+            if bool(fin.any()):                                                  # (part of the one sync below)
+                v = self.verts[fin]
+                lo, hi = v.aminmax(dim=0)
+                ext = (tri.amax(dim=1) - tri.amin(dim=1)).amax(dim=1)            # largest axis extent of every face's box
+                mean = torch.where(ok, ext, torch.zeros_like(ext)).double().sum() / ok.sum().clamp(min=1)
+                stats = torch.cat([torch.stack([lo, hi], 1).reshape(-1).double(), mean.reshape(1)]).cpu().tolist()
+        if stats is None:
+            _hip.check(lib.eslam_tri_grid_plan(0, None, 0.0, ctypes.byref(self.grid)), "eslam_tri_grid_plan")
+            return
+        _hip.check(lib.eslam_tri_grid_plan(n_faces, (ctypes.c_float * 6)(*stats[:6]), float(stats[6]), ctypes.byref(self.grid)),
+                   "eslam_tri_grid_plan")
+        total = torch.empty(2, dtype=torch.int64, device=self.device)
+        with _hip.on_device(self.device):
+            _hip.check(lib.eslam_tri_count(_hip.ptr(self.verts), n_verts, _hip.ptr(self.faces), n_faces, ctypes.byref(self.grid),
+                                           _hip.ptr(total), _hip.stream_handle(self.device)), "eslam_tri_count")
+        self.grid.entries, self.faces_entered = (int(x) for x in total.cpu().tolist())
+        if self.grid.entries == 0:
+            return
+        nbytes = int(lib.eslam_tri_workspace_bytes(ctypes.byref(self.grid)))
+        if nbytes < 0:
+            _hip.check(1, "eslam_tri_workspace_bytes")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with _hip.on_device(self.device):
+            _hip.check(lib.eslam_tri_build(_hip.ptr(self.verts), n_verts, _hip.ptr(self.faces), n_faces, ctypes.byref(self.grid),
+                                           _hip.ptr(self.ws), _hip.stream_handle(self.device)), "eslam_tri_build")
+
+    @property
+    def dims(self):
+        return tuple(self.grid.dims)
+
+    @property
+    def entries(self):
+        """The number of (face, cell) entries of the grid (a face is entered in every cell its box overlaps)."""
+        return int(self.grid.entries)
+
+    def query(self, q, max_dist=None, closest=False, sort=True):
+        """(dist float32 [Q], face int32 [Q]) or, with closest=True, (dist, face, closest float32 [Q,3]) on the mesh's
+        device: the distance to the nearest point of the mesh, the face it lies on (the smaller index among equal
+        distances) and that point.  max_dist: only faces with dist < max_dist count.  A query with none, or with a
+        non-finite coordinate, gets (inf, -1, NaN).  sort=False processes the queries in input order instead of cell
+        order (same results)."""
+        q = _gpu_points("q", q, self.device)
+        nq = q.shape[0]
+        dist = torch.full((nq,), float("inf"), device=self.device)
+        face = torch.full((nq,), -1, dtype=torch.int32, device=self.device)
+        near = torch.full((nq, 3), float("nan"), device=self.device) if closest else None
+        md = float("inf") if max_dist is None else float(max_dist)
+        if md != md:
+            raise ValueError("MeshDistance.query: max_dist is NaN")
+        if nq and self.grid.entries:
+            lib = _hip.lib()
+            qws = None
+            if sort:
+                qws = torch.empty(int(lib.eslam_tri_query_workspace_bytes(ctypes.byref(self.grid), nq)), dtype=torch.uint8,
+                                  device=self.device)
+            with _hip.on_device(self.device):
+                _hip.check(lib.eslam_tri_query(ctypes.byref(self.grid), _hip.ptr(self.ws), _hip.ptr(q), nq, md,
+                                               0 if sort else _hip.TRI_INPUT_ORDER, _hip.ptr(qws), _hip.ptr(dist),
+                                               _hip.ptr(face), _hip.ptr(near), _hip.stream_handle(self.device)),
+                           "eslam_tri_query")
+        return (dist, face, near) if closest else (dist, face)
+
+
 def sample_surface(verts, faces, n, seed=0):
     """(samples float64 [n,3], face_index int64 [n]) on verts' device, as trimesh.sample.sample_surface: faces picked
     with probability proportional to their area (float64 areas, cumulative sum, searchsorted of u * total, left side),

@@ -6,6 +6,7 @@ correspondence moments reduced on the GPU (ops.icp_moments) and the 3x3 solve on
 unseen-points test of a batch of candidate views (ops.views_see_points).
 
     python -m myslam_amd.src.tools.eval_recon --rec_mesh REC.ply --gt_mesh GT.ply -2d -3d
+    python -m myslam_amd.src.tools.eval_recon --rec_mesh REC.ply --gt_mesh GT.ply --report --exact --error_mesh OUT
 
 accuracy / completion / completion_ratio take numpy arrays or torch tensors [N,3] and return a float, as the reference's
 (eval_recon.py:21-39).  Deviations, 3D: the samples are drawn from a torch generator seeded with `seed` (the reconstructed
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from ..utils.Mesher import read_ply
+from ..utils.Mesher import read_ply, write_ply
 
 ICP_THRESHOLD = 0.1          # eval_recon.py:50
 ICP_MAX_ROUNDS = 30          # open3d ICPConvergenceCriteria defaults
@@ -152,6 +153,141 @@ def calc_3d_metric(rec_meshfile, gt_meshfile, align=True, num_points=450000):
     print('accuracy: ', r["accuracy"])
     print('completion: ', r["completion"])
     print('completion ratio: ', r["completion_ratio"])
+    return r
+
+
+# ----------------------------------------------------------------------------------------------
+# beyond the reference: F-score, normal consistency, exact point-to-mesh distances, error maps
+# ----------------------------------------------------------------------------------------------
+def f_score(d_rec_to_gt, d_gt_to_rec, threshold):
+    """(precision, recall, f) as fractions, from the distances of the reconstruction's points to the ground truth and of
+    the ground truth's points to the reconstruction (tensors or arrays on any device): precision = the share of the
+    first below `threshold` (strict, as completion_ratio), recall the share of the second, f = 2 p r / (p + r), 0 when
+    both are 0.  An empty side has share 0."""
+    def share(d):
+        d = torch.as_tensor(d).reshape(-1)
+        return int((d < threshold).sum()) / d.numel() if d.numel() else 0.0
+    p, r = share(d_rec_to_gt), share(d_gt_to_rec)
+    return p, r, (2.0 * p * r / (p + r) if p + r > 0 else 0.0)
+
+
+def normal_consistency(n_a, n_b):
+    """(mean |n_a . n_b| over the rows where both normals have a non-zero, finite length, each normalised in float64;
+    the number of rows used).  Rows left out are those with a zero or non-finite normal on either side: total - used.
+    No row used: (nan, 0).  Tensors or arrays [N,3] on any device."""
+    a = torch.as_tensor(n_a).to(torch.float64).reshape(-1, 3)
+    b = torch.as_tensor(n_b).to(a.device, torch.float64).reshape(-1, 3)
+    la, lb = a.norm(dim=1), b.norm(dim=1)
+    use = (la > 0) & (lb > 0) & torch.isfinite(la) & torch.isfinite(lb)
+    used = int(use.sum())
+    if used == 0:
+        return float("nan"), 0
+    dots = ((a[use] / la[use, None]) * (b[use] / lb[use, None])).sum(dim=1).abs()
+    return float(dots.mean()), used
+
+
+def face_normals(verts, faces):
+    """float64 [F,3] on verts' device: the unit normal (b - a) x (c - a) / |.| of every face, a zero row for a face of
+    zero (or non-finite) area."""
+    v = torch.as_tensor(verts).to(torch.float64).reshape(-1, 3)
+    f = torch.as_tensor(faces).to(v.device, torch.int64).reshape(-1, 3)
+    n = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    ln = n.norm(dim=1, keepdim=True)
+    ok = (ln > 0) & torch.isfinite(ln)
+    return torch.where(ok, n / torch.where(ok, ln, torch.ones_like(ln)), torch.zeros_like(n))
+
+
+def error_colors(dist, max_err, lut=None):
+    """uint8 [N,3] on dist's device: lut[floor(min(d / max_err, 1) * 255 + 0.5)] in float64, index 255 for an infinite
+    or NaN distance; lut = the committed plasma table (ops.load_plasma_lut) unless given."""
+    d = torch.as_tensor(dist).to(torch.float64).reshape(-1)
+    if lut is None:
+        lut = torch.from_numpy(ops.load_plasma_lut())
+    lut = torch.as_tensor(lut).to(d.device)
+    idx = torch.floor(torch.clamp(d / float(max_err), max=1.0) * 255.0 + 0.5)
+    idx = torch.where(torch.isfinite(d), idx, torch.full_like(idx, 255.0)).to(torch.int64)
+    return lut[idx]
+
+
+def _report_inputs(rec_v, rec_f, gt_v, gt_f, align, device):
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    rec = torch.as_tensor(rec_v).to(dev, torch.float64).reshape(-1, 3)
+    gt = torch.as_tensor(gt_v).to(dev, torch.float64).reshape(-1, 3)
+    rec_f, gt_f = torch.as_tensor(rec_f).to(dev), torch.as_tensor(gt_f).to(dev)
+    if align:
+        rec = _transform(icp(rec, gt)[0], rec)
+    return rec, rec_f, gt, gt_f
+
+
+def recon_report(rec_v, rec_f, gt_v, gt_f, align=True, num_points=450000, seed=0, exact=False, f_threshold=0.05, device=None):
+    """recon_metrics' three numbers and the metrics the reference lacks, from the same samples: {'accuracy',
+    'completion' (cm), 'completion_ratio' (%, 5 cm), 'chamfer' (cm, their mean), 'precision', 'recall', 'f_score' (%, at
+    f_threshold), 'normal_consistency' (mean |n . n'| of a sample's face normal and the other side's, both directions
+    averaged), 'normals_skipped' (rows without a normal on either side, both directions), 'exact'}.
+    exact=False: every sample is measured to the nearest SAMPLE of the other mesh (ops.NNGrid), as recon_metrics does -
+    the first three keys are recon_metrics' floats - and the other side's normal is that sample's face's.
+    exact=True: every sample is measured to the other MESH (ops.MeshDistance, float32 vertices) and the normal is the
+    returned face's: no sampling bias on the far side."""
+    rec, rec_f, gt, gt_f = _report_inputs(rec_v, rec_f, gt_v, gt_f, align, device)
+    rec_s, rec_fi = ops.sample_surface(rec, rec_f, num_points, seed)
+    gt_s, gt_fi = ops.sample_surface(gt, gt_f, num_points, seed + 1)
+    rec_pc, gt_pc = rec_s.float(), gt_s.float()
+    rec_n, gt_n = face_normals(rec, rec_f), face_normals(gt, gt_f)
+    if exact:
+        acc, acc_face = ops.MeshDistance(gt.float(), gt_f).query(rec_pc)
+        comp, comp_face = ops.MeshDistance(rec.float(), rec_f).query(gt_pc)
+    else:
+        acc, idx = ops.NNGrid(gt_pc).query(rec_pc)
+        acc_face = torch.where(idx >= 0, gt_fi[idx.long().clamp(min=0)], torch.full_like(gt_fi[:1], -1))
+        comp, idx = ops.NNGrid(rec_pc).query(gt_pc)
+        comp_face = torch.where(idx >= 0, rec_fi[idx.long().clamp(min=0)], torch.full_like(rec_fi[:1], -1))
+
+    def other(normals, face):          # the other side's normal, a zero row where no face was found
+        face = face.long()
+        return torch.where((face >= 0)[:, None], normals[face.clamp(min=0)], torch.zeros_like(normals[:1]))
+
+    nc_a, used_a = normal_consistency(rec_n[rec_fi], other(gt_n, acc_face))
+    nc_c, used_c = normal_consistency(gt_n[gt_fi], other(rec_n, comp_face))
+    p, r, f = f_score(acc, comp, f_threshold)
+    accuracy_cm, completion_cm = float(acc.double().mean()) * 100, float(comp.double().mean()) * 100
+    return {"accuracy": accuracy_cm, "completion": completion_cm,
+            "completion_ratio": int((comp < 0.05).sum()) / comp.numel() * 100,
+            "chamfer": 0.5 * (accuracy_cm + completion_cm), "precision": p * 100, "recall": r * 100, "f_score": f * 100,
+            "normal_consistency": 0.5 * (nc_a + nc_c), "normals_skipped": (acc.numel() - used_a) + (comp.numel() - used_c),
+            "exact": bool(exact)}
+
+
+def error_meshes(rec_v, rec_f, gt_v, gt_f, max_err=0.05, align=True, device=None):
+    """Per-vertex error maps: the exact distance (ops.MeshDistance) of every vertex of the (aligned) reconstruction to
+    the ground-truth mesh and of every ground-truth vertex to the reconstruction, coloured by error_colors(d, max_err).
+    Returns {'rec_colors', 'gt_colors' (uint8 [V,3]), 'rec_dist', 'gt_dist' (float32 [V], metres), 'rec_vertices'
+    (float64 [V,3], after the alignment)}, tensors on the GPU."""
+    rec, rec_f, gt, gt_f = _report_inputs(rec_v, rec_f, gt_v, gt_f, align, device)
+    rec_d = ops.MeshDistance(gt.float(), gt_f).query(rec.float())[0]
+    gt_d = ops.MeshDistance(rec.float(), rec_f).query(gt.float())[0]
+    return {"rec_colors": error_colors(rec_d, max_err), "gt_colors": error_colors(gt_d, max_err), "rec_dist": rec_d,
+            "gt_dist": gt_d, "rec_vertices": rec}
+
+
+def write_error_meshes(rec_meshfile, gt_meshfile, prefix, max_err=0.05, align=True):
+    """PREFIX_accuracy.ply: the (aligned) reconstruction coloured by its distance to the ground truth; PREFIX_completion.ply:
+    the ground truth coloured by its distance to the reconstruction (plasma, 0 .. max_err metres).  Returns the paths."""
+    rec_v, rec_f, _ = read_ply(rec_meshfile)
+    gt_v, gt_f, _ = read_ply(gt_meshfile)
+    e = error_meshes(rec_v, rec_f, gt_v, gt_f, max_err=max_err, align=align)
+    paths = (prefix + "_accuracy.ply", prefix + "_completion.ply")
+    write_ply(paths[0], e["rec_vertices"].cpu().numpy(), rec_f, colors=e["rec_colors"].cpu().numpy() / 255.0)
+    write_ply(paths[1], gt_v, gt_f, colors=e["gt_colors"].cpu().numpy() / 255.0)
+    return paths
+
+
+def print_report(rec_meshfile, gt_meshfile, exact=False, f_threshold=0.05, align=True, num_points=450000):
+    """recon_report of two mesh files, one `name: value` line per key."""
+    rec_v, rec_f, _ = read_ply(rec_meshfile)
+    gt_v, gt_f, _ = read_ply(gt_meshfile)
+    r = recon_report(rec_v, rec_f, gt_v, gt_f, align=align, num_points=num_points, exact=exact, f_threshold=f_threshold)
+    for k, v in r.items():
+        print(f"{k}: {v}")
     return r
 
 
@@ -361,7 +497,18 @@ if __name__ == '__main__':
     parser.add_argument('--gt_mesh', type=str, help='ground truth mesh file path')
     parser.add_argument('-2d', '--metric_2d', action='store_true', help='enable 2D metric')
     parser.add_argument('-3d', '--metric_3d', action='store_true', help='enable 3D metric')
+    parser.add_argument('--report', action='store_true', help='accuracy, completion, F-score, normal consistency: one '
+                        '"name: value" line per key')
+    parser.add_argument('--exact', action='store_true', help='--report measures to the other mesh, not to its samples')
+    parser.add_argument('--f_threshold', type=float, default=0.05, help='distance threshold (m) of precision / recall / F-score')
+    parser.add_argument('--error_mesh', type=str, default=None, metavar='PREFIX',
+                        help='write PREFIX_accuracy.ply and PREFIX_completion.ply, vertices coloured by exact distance')
+    parser.add_argument('--error_max', type=float, default=0.05, help='distance (m) at the top of the colour scale')
     args = parser.parse_args()
+    if args.report:
+        print_report(args.rec_mesh, args.gt_mesh, exact=args.exact, f_threshold=args.f_threshold)
+    if args.error_mesh:
+        write_error_meshes(args.rec_mesh, args.gt_mesh, args.error_mesh, max_err=args.error_max)
     if args.metric_3d:
         calc_3d_metric(args.rec_mesh, args.gt_mesh)
     if args.metric_2d:
